@@ -1,6 +1,6 @@
 """Headline benchmark: rendered frames/s at 512x512, RenderFormer-V1.1-swin-large (proxy shape), cbox.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cbox|c4|c5] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cbox|c4|c5] [--dump-outputs DIR] [--full] ...
 
 Workloads (all synthetic, seeded, inputs resident in HBM before the timed region):
 
@@ -20,10 +20,15 @@ Multi-GPU: one process per GPU.  Under ``torch.distributed.run`` the env (RANK/W
 ``--gpus`` must equal WORLD_SIZE; run directly with ``--gpus N > 1`` this script starts
 ``torch.distributed.run --nproc-per-node N`` itself (before any GPU call) and exits with its status.
 
-The JSON line carries a roofline object for the dominant kernel (stage-1 attention), each of its launches in
-the last timed step timed by HIP events that its own dispatch packet timestamps (hipExtLaunchKernel), the
-parity of the last GPU frame against the reference (the committed reference-generated fixture when the
-workload is that fixture's, and the oracle frame of the CPU baseline), and the CPU baseline itself: the oracle restatement of the reference (oracle/rf_ref.py,
+A plain run sets up, warms up, times the ``--steps`` steps, writes the last step's frames when ``--dump-outputs
+DIR`` is given (``DIR/frames.npy``, float32; inputs and weights are seeded, so two builds can be compared frame
+for frame) and prints one JSON line.  The line carries ``ms_per_step`` and a roofline object for the dominant
+kernel (stage-1 attention), each of its launches in the last timed step timed by HIP events that its own
+dispatch packet timestamps (hipExtLaunchKernel; no run of its own).
+
+``--full`` adds what takes work of its own after the timed region: the parity of the last GPU frame against the
+reference (the committed reference-generated fixture when the workload is that fixture's, and the oracle frame
+of the CPU baseline), and the CPU baseline itself: the oracle restatement of the reference (oracle/rf_ref.py,
 PyTorch CPU fp32) on a bounded sample of the same workload, rank 0 at N = 1 only.
 """
 from __future__ import annotations
@@ -61,7 +66,13 @@ def parse(argv=None):
     ap.add_argument("--res", type=int, default=None, help="default 512 (1024 for c5)")
     ap.add_argument("--views", type=int, default=None, help="default 1 (24 for c5)")
     ap.add_argument("--scenes", type=int, default=1, help="cbox: scenes per rank per step; c4: scenes per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the parity of the "
+                         "last frame against the reference fixture, the CPU baseline and the parity against its frame")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the frames of the last timed step to DIR/frames.npy (float32; a fixed seeded "
+                         "sample of the values, DIR/frames_sample.npy, when they exceed 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=3)
     ap.add_argument("--profile", action="store_true", help="short run for rocprofv3 (no cpu baseline)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo: CPU-side tests)")
@@ -74,6 +85,8 @@ def parse(argv=None):
                                                         "MX fp8 GEMMs (the subset inside the 1e-3 bar); roofline then "
                                                         "reports the stage-2 W2 fp8 GEMM")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.res is None:
         a.res = 1024 if a.workload == "c5" else 512
     if a.views is None:
@@ -157,6 +170,24 @@ def fixture_parity(args, frame):
     ref = torch.from_numpy(np.load(path)["hdr"]).double()
     got = frame.detach().double().cpu().reshape(ref.shape)
     return float((got - ref).norm() / ref.norm())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, frames):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the gathered HDR frames
+    [frames, res, res, channels], as float32 in DIR/frames.npy; past 64 MB a fixed seeded sample of the
+    flattened values (the same positions on every run of the same arguments) in DIR/frames_sample.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arr = frames.detach().to(torch.float32).cpu().contiguous().numpy()
+    if arr.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "frames.npy"), arr)
+        return
+    flat = arr.reshape(-1)
+    pos = np.sort(np.random.default_rng(0).choice(flat.size, DUMP_LIMIT_BYTES // 8, replace=False))
+    np.save(os.path.join(directory, "frames_sample.npy"), flat[pos])
 
 
 def main():
@@ -352,6 +383,8 @@ def main():
     if args.dump and rank == 0:
         import numpy as np
         np.save(args.dump, out.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
         if args.workload == "cbox":
             wl = (f"cbox-sized scene N={args.tris}, {args.res}x{args.res}, {args.views} view(s) x {args.scenes} "
@@ -407,10 +440,11 @@ def main():
             "parity": {"vs_reference_fixture_rel_l2": None, "vs_oracle_rel_l2": None},
             "cpu_baseline": None,
         }
-        if args.workload == "cbox":
+        if args.full and args.workload == "cbox":
             fp = fixture_parity(args, out[:n_per_rank])
             rec["parity"]["vs_reference_fixture_rel_l2"] = None if fp is None else float(f"{fp:.3e}")
-        if world == 1 and args.workload == "cbox" and not args.no_cpu_baseline and not args.profile:
+        if (args.full and world == 1 and args.workload == "cbox" and not args.no_cpu_baseline
+                and not args.profile):
             cpu_batch = {k: v for k, v in hosts[0].items() if k != "tex_channels"}
             rec["cpu_baseline"], ref = cpu_baseline(cfg, sd, cpu_batch, args.res, args.cpu_frames)
             got = out.detach().double().cpu().reshape(ref.shape)

@@ -32,6 +32,34 @@ def test_gpus_n_starts_n_ranks(monkeypatch):
     assert "--master-addr=127.0.0.1" in cmd and cmd[-4:] == ["--gpus", "4", "--steps", "3"]
 
 
+def test_plain_run_is_the_default():
+    """--full (parity, CPU baseline) is opt-in; --steps is the number of timed steps and must be positive."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: the whole array as float32 under the size limit; past it the same seeded sample every time."""
+    import bench
+    import torch
+    frames = torch.arange(2 * 8 * 8 * 3, dtype=torch.float64).reshape(2, 8, 8, 3) / 7
+    bench.dump_outputs(str(tmp_path / "a"), frames)
+    got = np.load(tmp_path / "a" / "frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frames.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 256)
+    bench.dump_outputs(str(tmp_path / "b"), frames)
+    bench.dump_outputs(str(tmp_path / "c"), frames + 1)
+    sb, sc = np.load(tmp_path / "b" / "frames_sample.npy"), np.load(tmp_path / "c" / "frames_sample.npy")
+    assert not (tmp_path / "b" / "frames.npy").exists()
+    assert sb.dtype == np.float32 and sb.nbytes <= 256 and sb.size == 32
+    assert np.allclose(sc - sb, 1.0) and np.all(np.diff(sb) > 0)  # the same, ordered positions in both runs
+    assert np.isin(sb, got.reshape(-1)).all()
+
+
 def _bench(tmp_path, tag, gpus, extra):
     dump = str(tmp_path / f"{tag}.npy")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "0",

@@ -1,8 +1,8 @@
 # One runner for every GPU-box job (run through gpurun from the repo root):
 #   bash tools/gpu.sh <task> <tag> [args...]      outputs under gpurun_out/<tag>/
 # tasks
-#   check            GPU test suite + default bench (20 steps)
-#   round            round evidence: tests, bench (+ CPU baseline), smoke, kernel-trace stats, HBM traffic
+#   check            GPU test suite + default bench (20 steps, --full: parity + CPU baseline)
+#   round            round evidence: tests, bench (--full: parity + CPU baseline), smoke, kernel-trace stats, HBM traffic
 #                    (FETCH_SIZE / WRITE_SIZE, one --pmc pass each), attention MFMA counters and in-kernel clock
 #   roundnt          the same without the GPU test suite (run `check` or the suite on its own first)
 #   prof [bench args]  rocprofv3 kernel-trace stats of a short bench run
@@ -49,10 +49,10 @@ prof_run() {  # rocprofv3 needs a cwd and TMPDIR it can write
 case $TASK in
 check)
     timeout -k 10 900 $T tests -m gpu > $O/tests.log 2>&1
-    timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ;;
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ;;
 round|roundnt)
     if [ $TASK = round ]; then timeout -k 10 900 $T tests -m gpu > $O/tests.log 2>&1; fi
-    timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+    timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
     prof_run timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 $R/bench.py --profile --steps 5 --warmup 2 > $O/prof.log 2>&1
     prof_run timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 $R/bench.py --profile --steps 2 --warmup 1 > $O/pmc_fetch.log 2>&1
