@@ -31,6 +31,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "env.h"
 
 namespace {
 
@@ -3032,9 +3033,8 @@ using T64x128c = Tile<64, 128, 2, 2, 6>;
 // column, and each A panel is fetched once per XCD (rf_gemm_mx8 W2 at 98,304 rows: 845 -> 748 us, the f16 engine
 // 814 -> 762: profiles/r6_mx8_raster.txt)
 int pick_group_m(int tiles_m, int tiles_n, int bm, int bn, int64_t per_xcd, int64_t a_bytes = 0) {
-    if (const char* env = getenv("RF_GEMM_GROUP_M")) return std::max(1, std::min(tiles_m, atoi(env)));
-    static const bool stream_raster = !getenv("RF_GEMM_STREAM_RASTER") || atoi(getenv("RF_GEMM_STREAM_RASTER")) != 0;
-    if (stream_raster && a_bytes > (192ll << 20) && tiles_n <= 8) return std::max(1, std::min(tiles_m, 32 / tiles_n));
+    if (rf::env_set("RF_GEMM_GROUP_M")) return std::max(1, std::min(tiles_m, rf::env_int("RF_GEMM_GROUP_M", 0)));
+    if (RF_ENV_ONCE("RF_GEMM_STREAM_RASTER", 1) != 0 && a_bytes > (192ll << 20) && tiles_n <= 8) return std::max(1, std::min(tiles_m, 32 / tiles_n));
     const double g = std::sqrt((double)per_xcd * bn / bm);
     int gm = (int)(g + 0.5);
     gm = std::max(1, std::min(gm, tiles_m));
@@ -3082,8 +3082,7 @@ int launch_halo(EngineArgs a, void* stream, const char* what) {
 template <class C, int NTERM, bool GATHER>
 int launch_conv(EngineArgs& a, void* stream, const char* what) {
     if constexpr (GATHER && NTERM == P_F16) {
-        const char* env = getenv("RF_CONV_HALO");
-        const bool want = env ? atoi(env) != 0 : (C::BM == 128 && C::NWAVE == 4);
+        const bool want = rf::env_int("RF_CONV_HALO", C::BM == 128 && C::NWAVE == 4) != 0;
         if (want && halo_ok<C>(a)) return launch_halo<C, E_CONV>(a, stream, what);
     }
     return launch<C, E_CONV, NTERM, GATHER>(a, stream, what);
@@ -3112,20 +3111,46 @@ int sk_setup(EngineArgs& p, void* workspace, void* stream) {
     p.err = rf::device_error_word();
     p.spin = rf::spin_limit();
     // diagnostics: stamps in the last 256 KiB of the partial area (tools/kbench.py skstamps)
-    static const bool stamps = getenv("RF_GEMM_STAMPS") && atoi(getenv("RF_GEMM_STAMPS")) != 0;
-    p.stamps = stamps ? (uint64_t*)(p.sk_part + SK_PART_FLOATS - 65536) : nullptr;
+    p.stamps = RF_ENV_ONCE("RF_GEMM_STAMPS", 0) != 0 ? (uint64_t*)(p.sk_part + SK_PART_FLOATS - 65536) : nullptr;
     return RF_OK;
+}
+
+// The one switch from a runtime RF_EPI_BF16 / F32 / ADD_F32 / SWIGLU (validated by the caller) to the kernels'
+// compile-time Epi: f(std::integral_constant<int, E_*>{}), so a launcher family is one line at its call site:
+//   with_epi(epilogue, [&](auto e) { return launch<C, decltype(e)::value, NT>(p, stream, what); })
+template <class F>
+int with_epi(int epilogue, F&& f) {
+    switch (epilogue) {
+        case RF_EPI_BF16: return f(std::integral_constant<int, E_BF16>{});
+        case RF_EPI_F32: return f(std::integral_constant<int, E_F32>{});
+        case RF_EPI_ADD_F32: return f(std::integral_constant<int, E_ADD>{});
+        default: return f(std::integral_constant<int, E_SWIGLU>{});
+    }
+}
+
+// the operand and output fields every dense entry point sets (rf_gemm_*, rf_gemm_qk_rope, rf_gemm_mx8)
+inline void dense_args(EngineArgs& p, const void* a, int64_t lda, const void* w, int64_t ldw, int m, int n, int k,
+                       void* c, int64_t ldc) {
+    p.a = (const bf16_t*)a;
+    p.lda = lda;
+    p.w = (const bf16_t*)w;
+    p.ldw = ldw;
+    p.m = m;
+    p.n = n;
+    p.k = k;
+    p.c = c;
+    p.ldc = ldc;
 }
 
 
 // Stream-K grid for the 128x128 tile, or 0 for the data-parallel launch: used when whole-tile
 // rounds of 2 blocks per CU would leave >10% of the slots idle and each block keeps >= 8 K-steps.
 int sk_grid(int m, int n, int k) {
-    const char* env = getenv("RF_GEMM_SK");
+    const bool env = rf::env_set("RF_GEMM_SK");
     int grid = 2 * 256;
     if (!env) return 0;  // opt-in until validated on the GPU
     if (env) {
-        grid = atoi(env);
+        grid = rf::env_int("RF_GEMM_SK", 0);
         if (grid <= 0) return 0;
         grid = grid > SK_MAX_GRID ? SK_MAX_GRID : grid;
     }
@@ -3135,6 +3160,37 @@ int sk_grid(int m, int n, int k) {
     if (!env && (eff >= 0.9 || tiles * (k / BK) < 8LL * grid)) return 0;
     return grid;
 }
+
+// Tile codes: what RF_GEMM_TILE=<number> selects (tests and tools/kbench.py pass these numbers) and pick_cfg
+// returns.  P = phased loop (two LDS buffers), P3 = phased with three buffers, R = LDS-ring engine; TileTable below
+// has each code's loop, preconditions and fp16-operand support.  Any other number runs on TC_R128.
+enum TileCode : int {
+    TC_R128 = 128,         // ring 128x128, 4 waves, 3 stages: the default and every code's fall-through
+    TC_P256 = 256,         // phased 256x256; without use_phased the ring's 256x256 (8 waves, 4 stages)
+    TC_R64 = 642,          // ring 64x256, 8 waves
+    TC_P64 = 643,          // phased 64x256
+    TC_R64w4 = 644,        // ring 64x256, 4 waves
+    TC_P3_64 = 645,        // phased3 64x256
+    TC_R64s6 = 646,        // ring 64x256, 6 stages
+    TC_R96 = 962,          // ring 96x256
+    TC_P96 = 963,          // phased 96x256
+    TC_P3_96 = 964,        // phased3 96x256
+    TC_R96s5 = 965,        // ring 96x256, 5 stages
+    TC_R96s6 = 966,        // ring 96x256, 6 stages
+    TC_P128 = 1282,        // phased 128x256
+    TC_P3_128 = 1283,      // phased3 128x256
+    TC_R128s4 = 1284,      // ring 128x128, 4 stages
+    TC_R128s5 = 1285,      // ring 128x128, 5 stages
+    TC_R128s6 = 1286,      // ring 128x128, 6 stages
+    TC_R128w8s6 = 1288,    // ring 128x128, 8 waves, 6 stages
+    TC_R256x128 = 2561,    // ring 256x128, 8 waves
+    TC_R64k2 = 6423,       // ring 64x256, 64-deep steps
+    TC_R64w4k2 = 6443,     // ring 64x256, 4 waves, 64-deep steps
+    TC_R96k2 = 9623,       // ring 96x256, 64-deep steps
+    TC_R128k2s3 = 12823,   // ring 128x128, 64-deep steps, 3 stages
+    TC_R128k2s4 = 12824,   // ring 128x128, 64-deep steps, 4 stages
+    TC_R128w8k2 = 12884,   // ring 128x128, 8 waves, 64-deep steps, 4 stages
+};
 
 // Tile choice by a measured cost model (tools/kbench.py coldgemm: operands rotated over > 512 MB so every call
 // reads them from HBM, as in the frame where each layer's weights are read once; profiles/r2_gemm_cold.log).
@@ -3148,9 +3204,8 @@ int sk_grid(int m, int n, int k) {
 //   12884 ring   128x128, 8 waves, 64-deep steps, 4 stages   6.8 + 10.9   add 5
 //   128   ring   128x128, 4 waves: 5.5 + 13.1 at <= 256 tiles, else two blocks per CU 11 + 14 per 512
 int pick_cfg(int m, int n, int k, int epilogue = RF_EPI_BF16) {
-    if (const char* env = getenv("RF_GEMM_TILE")) return atoi(env);
-    const char* ph = getenv("RF_GEMM_PHASED");
-    const bool phased = n % 256 == 0 && k % 64 == 0 && (!ph || atoi(ph) != 0);
+    if (rf::env_set("RF_GEMM_TILE")) return rf::env_int("RF_GEMM_TILE", 0);
+    const bool phased = n % 256 == 0 && k % 64 == 0 && rf::env_int("RF_GEMM_PHASED", 1) != 0;
     const double kk = k / 1024.0;
     const bool add = epilogue == RF_EPI_ADD_F32;
     auto cost = [&](int bm, int bn, int slots, double fixed, double per_k, double add_cost) {
@@ -3158,7 +3213,7 @@ int pick_cfg(int m, int n, int k, int epilogue = RF_EPI_BF16) {
         const int64_t rounds = (tiles + 256 * slots - 1) / (256 * slots);
         return rounds * (fixed + per_k * kk + (add ? add_cost : 0.0));
     };
-    int best = 128;
+    int best = TC_R128;
     const int64_t t128 = (int64_t)((m + 127) / 128) * (n / 128);
     double best_c = t128 <= 256 ? cost(128, 128, 1, 5.5, 13.1, 5.0) : cost(128, 128, 2, 11.0, 14.0, 5.0);
     auto consider = [&](int cfg, double c) {
@@ -3167,13 +3222,13 @@ int pick_cfg(int m, int n, int k, int epilogue = RF_EPI_BF16) {
             best = cfg;
         }
     };
-    if (k % 64 == 0) consider(12884, cost(128, 128, 1, 6.8, 10.9, 5.0));
-    if (n % 256 == 0) consider(962, cost(96, 256, 1, 2.2, 16.5, 13.0));
+    if (k % 64 == 0) consider(TC_R128w8k2, cost(128, 128, 1, 6.8, 10.9, 5.0));
+    if (n % 256 == 0) consider(TC_R96, cost(96, 256, 1, 2.2, 16.5, 13.0));
     if (phased) {
-        consider(256, cost(256, 256, 1, 11.0, 20.4, 5.0));
-        consider(1282, cost(128, 256, 1, 2.3, 18.4, 5.0));
-        consider(964, cost(96, 256, 1, 6.0, 14.4, 5.0));
-        consider(645, cost(64, 256, 1, 6.5, 11.8, 5.0));
+        consider(TC_P256, cost(256, 256, 1, 11.0, 20.4, 5.0));
+        consider(TC_P128, cost(128, 256, 1, 2.3, 18.4, 5.0));
+        consider(TC_P3_96, cost(96, 256, 1, 6.0, 14.4, 5.0));
+        consider(TC_P3_64, cost(64, 256, 1, 6.5, 11.8, 5.0));
     }
     return best;
 }
@@ -3520,8 +3575,7 @@ __global__ __launch_bounds__(256) void quant_mx8_kernel(const bf16_t* __restrict
 // one block per CU looping over whole tiles, each block prefetching its next tile's first K-tiles before the
 // current tile's epilogue (phased_sk_kernel, p.persist) instead of one block per tile.
 bool persist_on() {
-    static const bool on = !getenv("RF_GEMM_PERSIST") || atoi(getenv("RF_GEMM_PERSIST")) != 0;
-    return on;
+    return RF_ENV_ONCE("RF_GEMM_PERSIST", 1) != 0;
 }
 
 // A tile count that is not a whole number of 256-block rounds (the stage-1 SwiGLU W13: 736 tiles) runs one block per
@@ -3529,8 +3583,7 @@ bool persist_on() {
 // prefetch costs registers (phased_sk_kernel spills at 256 VGPRs, phased_kernel<256> does not).  RF_GEMM_PERSIST_RAGGED=1
 // restores the persistent launch there (A/B: profiles/r6_w13_persist_ab.txt).
 bool persist_ragged() {
-    static const bool on = getenv("RF_GEMM_PERSIST_RAGGED") && atoi(getenv("RF_GEMM_PERSIST_RAGGED")) != 0;
-    return on;
+    return RF_ENV_ONCE("RF_GEMM_PERSIST_RAGGED", 0) != 0;
 }
 
 template <int EPI, int NTERM, bool GATHER, int BM = 256>
@@ -3552,8 +3605,7 @@ int launch_phased(EngineArgs a, void* stream, const char* what) {
 #ifdef RF_STUDY
 // phased3 loop's L2 run-ahead distance (K-tiles; 0 = off): RF_GEMM_L2PF (study build)
 int l2pf_dist() {
-    const char* env = getenv("RF_GEMM_L2PF");
-    return env ? std::max(0, std::min(8, atoi(env))) : 0;
+    return std::max(0, std::min(8, rf::env_int("RF_GEMM_L2PF", 0)));
 }
 #endif
 
@@ -3569,16 +3621,6 @@ int launch_phased3(EngineArgs a, void* stream, const char* what) {
     return rf::check_launch(what);
 }
 
-template <int BM, int NT = 1>
-int run_phased3(const EngineArgs& p, int epilogue, void* stream) {
-    switch (epilogue) {
-        case RF_EPI_BF16: return launch_phased3<E_BF16, BM, NT>(p, stream, "rf_gemm");
-        case RF_EPI_F32: return launch_phased3<E_F32, BM, NT>(p, stream, "rf_gemm");
-        case RF_EPI_ADD_F32: return launch_phased3<E_ADD, BM, NT>(p, stream, "rf_gemm");
-        default: return launch_phased3<E_SWIGLU, BM, NT>(p, stream, "rf_gemm");
-    }
-}
-
 template <int EPI, int NT = 1>
 int launch_phased_sk(EngineArgs a, int grid, void* stream, const char* what) {
     const int tiles_m = (a.m + 255) / 256, tiles_n = a.n / 256;
@@ -3589,116 +3631,100 @@ int launch_phased_sk(EngineArgs a, int grid, void* stream, const char* what) {
 
 // the phased 256x256 loop replaces the ring engine's 256x256 tile (RF_GEMM_PHASED=0 restores it)
 bool use_phased(int n, int k) {
-    const char* env = getenv("RF_GEMM_PHASED");
-    return (!env || atoi(env) != 0) && n % 256 == 0 && k % 64 == 0;
+    return rf::env_int("RF_GEMM_PHASED", 1) != 0 && n % 256 == 0 && k % 64 == 0;
 }
 
-template <class C, int NT = 1>
-int run_dp_cfg(const EngineArgs& p, int epilogue, void* stream) {
-    switch (epilogue) {
-        case RF_EPI_BF16: return launch<C, E_BF16, NT>(p, stream, "rf_gemm");
-        case RF_EPI_F32: return launch<C, E_F32, NT>(p, stream, "rf_gemm");
-        case RF_EPI_ADD_F32: return launch<C, E_ADD, NT>(p, stream, "rf_gemm");
-        default: return launch<C, E_SWIGLU, NT>(p, stream, "rf_gemm");
+// The loop a tile code runs on
+template <class C>
+struct Ring {};  // engine_kernel<C, ...>: the LDS-ring main loop on tile C
+template <int BM>
+struct Phased {};  // phased_kernel<BM, ...>, two LDS buffers (BM = 256: or its persistent form, launch_phased)
+template <int BM>
+struct Phased3 {};  // phased3_kernel<BM, ...>, three LDS buffers
+
+// What a row needs of the problem before it may run; a code whose row fails falls through to TC_R128
+enum Pre { PRE_NONE = 0, PRE_N256 = 1, PRE_K64 = 2, PRE_PHASED = 4 };  // N % 256 == 0, K % 64 == 0, use_phased(n, k)
+
+bool pre_ok(int pre, const EngineArgs& p) {
+    return (!(pre & PRE_N256) || p.n % 256 == 0) && (!(pre & PRE_K64) || p.k % 64 == 0) &&
+           (!(pre & PRE_PHASED) || use_phased(p.n, p.k));
+}
+
+// One row per tile code: the loop, its preconditions, and whether the fp16-operand instantiation exists (rf_gemm_f16
+// runs a code without one on TC_R128).  Rows are tried in order and the first whose code and preconditions match
+// runs, which matters for TC_P256 alone: phased when use_phased holds, else the ring's 256x256 tile.
+template <int CODE, class LOOP, int PRE, bool F16>
+struct Row {};
+template <class... R>
+struct Rows {};
+
+using TileTable = Rows<
+    //  code            loop                              preconditions        fp16
+    Row<TC_P256,        Phased<256>,                      PRE_PHASED,          true>,
+    Row<TC_P128,        Phased<128>,                      PRE_PHASED,          true>,
+    Row<TC_P256,        Ring<T256>,                       PRE_N256,            false>,
+    Row<TC_R128s4,      Ring<Tile<128, 128, 2, 2, 4>>,    PRE_NONE,            false>,
+    Row<TC_R128s5,      Ring<Tile<128, 128, 2, 2, 5>>,    PRE_NONE,            false>,
+    Row<TC_R256x128,    Ring<T256x128>,                   PRE_NONE,            false>,
+    Row<TC_R96,         Ring<T96x256>,                    PRE_N256,            true>,
+    Row<TC_R64,         Ring<T64x256>,                    PRE_N256,            false>,
+    Row<TC_P3_128,      Phased3<128>,                     PRE_PHASED,          true>,
+    Row<TC_P3_96,       Phased3<96>,                      PRE_PHASED,          true>,
+    Row<TC_P3_64,       Phased3<64>,                      PRE_PHASED,          true>,
+    Row<TC_P96,         Phased<96>,                       PRE_PHASED,          false>,
+    Row<TC_P64,         Phased<64>,                       PRE_PHASED,          false>,
+    Row<TC_R64w4,       Ring<T64x256w4>,                  PRE_N256,            false>,
+    Row<TC_R96s5,       Ring<T96x256s5>,                  PRE_N256,            false>,
+    Row<TC_R96s6,       Ring<T96x256s6>,                  PRE_N256,            false>,
+    Row<TC_R64s6,       Ring<T64x256s6>,                  PRE_N256,            false>,
+    Row<TC_R128s6,      Ring<T128s6>,                     PRE_NONE,            false>,
+    Row<TC_R128w8s6,    Ring<T128w8s6>,                   PRE_NONE,            false>,
+    Row<TC_R128k2s3,    Ring<T128k2s3>,                   PRE_K64,             false>,
+    Row<TC_R128k2s4,    Ring<T128k2s4>,                   PRE_K64,             false>,
+    Row<TC_R128w8k2,    Ring<T128w8k2s4>,                 PRE_K64,             true>,
+    Row<TC_R96k2,       Ring<T96x256k2>,                  PRE_K64 | PRE_N256,  false>,
+    Row<TC_R64k2,       Ring<T64x256k2>,                  PRE_K64 | PRE_N256,  false>,
+    Row<TC_R64w4k2,     Ring<T64x256w4k2>,                PRE_K64 | PRE_N256,  false>,
+    Row<TC_R128,        Ring<T128>,                       PRE_NONE,            true>>;
+
+// NT: the operand precision (1 = bf16, P_F16 = fp16)
+template <int NT, class C>
+int run_loop(Ring<C>, const EngineArgs& p, int epilogue, void* stream) {
+    return with_epi(epilogue, [&](auto e) { return launch<C, decltype(e)::value, NT>(p, stream, "rf_gemm"); });
+}
+template <int NT, int BM>
+int run_loop(Phased<BM>, const EngineArgs& p, int epilogue, void* stream) {
+    return with_epi(epilogue, [&](auto e) {
+        return launch_phased<decltype(e)::value, NT, false, BM>(p, stream, NT == P_F16 ? "rf_gemm_f16" : "rf_gemm_bf16");
+    });
+}
+template <int NT, int BM>
+int run_loop(Phased3<BM>, const EngineArgs& p, int epilogue, void* stream) {
+    return with_epi(epilogue, [&](auto e) { return launch_phased3<decltype(e)::value, BM, NT>(p, stream, "rf_gemm"); });
+}
+
+// true (and the launch's status in rc) when this row serves cfg
+template <int NT, int CODE, class LOOP, int PRE, bool F16>
+bool try_row(Row<CODE, LOOP, PRE, F16>, int cfg, const EngineArgs& p, int epilogue, void* stream, int& rc) {
+    if constexpr (NT == P_F16 && !F16) {
+        return false;
+    } else {
+        if (cfg != CODE || !pre_ok(PRE, p)) return false;
+        rc = run_loop<NT>(LOOP{}, p, epilogue, stream);
+        return true;
     }
 }
 
-// fp16 operands (rf_gemm_f16): the loops pick_cfg chooses from, each with fp16 MFMAs (same rate as bf16)
-int run_dp_f16(int cfg, const EngineArgs& p, int epilogue, void* stream) {
-    constexpr int NT = P_F16;
-    if (use_phased(p.n, p.k)) {
-        if (cfg == 256) {
-            switch (epilogue) {
-                case RF_EPI_BF16: return launch_phased<E_BF16, NT, false>(p, stream, "rf_gemm_f16");
-                case RF_EPI_F32: return launch_phased<E_F32, NT, false>(p, stream, "rf_gemm_f16");
-                case RF_EPI_ADD_F32: return launch_phased<E_ADD, NT, false>(p, stream, "rf_gemm_f16");
-                default: return launch_phased<E_SWIGLU, NT, false>(p, stream, "rf_gemm_f16");
-            }
-        }
-        if (cfg == 1282) {
-            switch (epilogue) {
-                case RF_EPI_BF16: return launch_phased<E_BF16, NT, false, 128>(p, stream, "rf_gemm_f16");
-                case RF_EPI_F32: return launch_phased<E_F32, NT, false, 128>(p, stream, "rf_gemm_f16");
-                case RF_EPI_ADD_F32: return launch_phased<E_ADD, NT, false, 128>(p, stream, "rf_gemm_f16");
-                default: return launch_phased<E_SWIGLU, NT, false, 128>(p, stream, "rf_gemm_f16");
-            }
-        }
-        if (cfg == 1283) return run_phased3<128, NT>(p, epilogue, stream);
-        if (cfg == 964) return run_phased3<96, NT>(p, epilogue, stream);
-        if (cfg == 645) return run_phased3<64, NT>(p, epilogue, stream);
-    }
-    if (cfg == 962 && p.n % 256 == 0) return run_dp_cfg<T96x256, NT>(p, epilogue, stream);
-    if (cfg == 12884 && p.k % 64 == 0) return run_dp_cfg<T128w8k2s4, NT>(p, epilogue, stream);
-    return run_dp_cfg<T128, NT>(p, epilogue, stream);
+// the data-parallel launch of tile code cfg (any integer: one that no row serves runs on TC_R128)
+template <int NT, class... R>
+int run_dp(Rows<R...>, int cfg, const EngineArgs& p, int epilogue, void* stream) {
+    int rc = RF_OK;
+    if ((try_row<NT>(R{}, cfg, p, epilogue, stream, rc) || ...)) return rc;
+    return run_loop<NT>(Ring<T128>{}, p, epilogue, stream);
 }
 
-// cfg codes: 128 = T128, 256 = T256 (needs N % 256 == 0), 1284 / 1285 = 128x128 with a 4 / 5-stage ring,
-// 2561 = 256x128 (8 waves)
-int run_dp(int cfg, const EngineArgs& p, int epilogue, void* stream) {
-    if (cfg == 256 && use_phased(p.n, p.k)) {
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_phased<E_BF16, 1, false>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_phased<E_F32, 1, false>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_phased<E_ADD, 1, false>(p, stream, "rf_gemm_bf16");
-            default: return launch_phased<E_SWIGLU, 1, false>(p, stream, "rf_gemm_bf16");
-        }
-    }
-    if (cfg == 1282 && use_phased(p.n, p.k)) {
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_phased<E_BF16, 1, false, 128>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_phased<E_F32, 1, false, 128>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_phased<E_ADD, 1, false, 128>(p, stream, "rf_gemm_bf16");
-            default: return launch_phased<E_SWIGLU, 1, false, 128>(p, stream, "rf_gemm_bf16");
-        }
-    }
-    if (cfg == 256 && p.n % 256 == 0) return run_dp_cfg<T256>(p, epilogue, stream);
-    if (cfg == 1284) return run_dp_cfg<Tile<128, 128, 2, 2, 4>>(p, epilogue, stream);
-    if (cfg == 1285) return run_dp_cfg<Tile<128, 128, 2, 2, 5>>(p, epilogue, stream);
-    if (cfg == 2561) return run_dp_cfg<T256x128>(p, epilogue, stream);
-    if (cfg == 962 && p.n % 256 == 0) return run_dp_cfg<T96x256>(p, epilogue, stream);
-    if (cfg == 642 && p.n % 256 == 0) return run_dp_cfg<T64x256>(p, epilogue, stream);
-    if (use_phased(p.n, p.k)) {  // three-buffer phased short tiles
-        if (cfg == 1283) return run_phased3<128>(p, epilogue, stream);
-        if (cfg == 964) return run_phased3<96>(p, epilogue, stream);
-        if (cfg == 645) return run_phased3<64>(p, epilogue, stream);
-    }
-    if (cfg == 963 && use_phased(p.n, p.k)) {  // phased 96x256
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_phased<E_BF16, 1, false, 96>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_phased<E_F32, 1, false, 96>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_phased<E_ADD, 1, false, 96>(p, stream, "rf_gemm_bf16");
-            default: return launch_phased<E_SWIGLU, 1, false, 96>(p, stream, "rf_gemm_bf16");
-        }
-    }
-    if (cfg == 643 && use_phased(p.n, p.k)) {  // phased 64x256
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_phased<E_BF16, 1, false, 64>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_phased<E_F32, 1, false, 64>(p, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_phased<E_ADD, 1, false, 64>(p, stream, "rf_gemm_bf16");
-            default: return launch_phased<E_SWIGLU, 1, false, 64>(p, stream, "rf_gemm_bf16");
-        }
-    }
-    if (cfg == 644 && p.n % 256 == 0) return run_dp_cfg<T64x256w4>(p, epilogue, stream);
-    if (cfg == 965 && p.n % 256 == 0) return run_dp_cfg<T96x256s5>(p, epilogue, stream);
-    if (cfg == 966 && p.n % 256 == 0) return run_dp_cfg<T96x256s6>(p, epilogue, stream);
-    if (cfg == 646 && p.n % 256 == 0) return run_dp_cfg<T64x256s6>(p, epilogue, stream);
-    if (cfg == 1286) return run_dp_cfg<T128s6>(p, epilogue, stream);
-    if (cfg == 1288) return run_dp_cfg<T128w8s6>(p, epilogue, stream);
-    if (p.k % 64 == 0) {
-        if (cfg == 12823) return run_dp_cfg<T128k2s3>(p, epilogue, stream);
-        if (cfg == 12824) return run_dp_cfg<T128k2s4>(p, epilogue, stream);
-        if (cfg == 12884) return run_dp_cfg<T128w8k2s4>(p, epilogue, stream);
-        if (cfg == 9623 && p.n % 256 == 0) return run_dp_cfg<T96x256k2>(p, epilogue, stream);
-        if (cfg == 6423 && p.n % 256 == 0) return run_dp_cfg<T64x256k2>(p, epilogue, stream);
-        if (cfg == 6443 && p.n % 256 == 0) return run_dp_cfg<T64x256w4k2>(p, epilogue, stream);
-    }
-    return run_dp_cfg<T128>(p, epilogue, stream);
-}
-
-bool sk256(int m, int n, int k) {
-    if (const char* env = getenv("RF_GEMM_SK256")) return atoi(env) != 0;
-    return false;  // the ring engine's 256x256 stream-K: superseded by the phased one, kept for A/B
-}
+// the ring engine's 256x256 stream-K: superseded by the phased one, kept for A/B (off unless RF_GEMM_SK256=1)
+bool sk256(int m, int n, int k) { return rf::env_int("RF_GEMM_SK256", 0) != 0; }
 
 // Phased 256x256 stream-K over one block per CU (RF_GEMM_SKPH=1/0 forces it on/off).  With partial tiles
 // its fix-up costs ~5-10 us per block, and the 128x256 phased tile beat it on every such shape measured
@@ -3707,7 +3733,7 @@ bool sk256(int m, int n, int k) {
 // (stage-2 W13 4096x8192x1024: 68 vs 72.5 us), so that case is the default.
 bool skph(int m, int n, int k) {
     if (!use_phased(n, k)) return false;
-    if (const char* env = getenv("RF_GEMM_SKPH")) return atoi(env) != 0;
+    if (rf::env_set("RF_GEMM_SKPH")) return rf::env_int("RF_GEMM_SKPH", 0) != 0;
     const int64_t tiles = (int64_t)((m + 255) / 256) * (n / 256);
     return n % 256 == 0 && tiles >= 512 && tiles % 256 == 0;
 }
@@ -3721,7 +3747,7 @@ extern "C" int64_t rf_gemm_workspace_bytes(void) { return SK_WS_BYTES; }
 // Needs K % 128 == 0, a column-tile multiple of N for the SwiGLU epilogue, and operands addressable by 32-bit
 // buffer offsets.
 static int quad_tile() {
-    const char* env = getenv("RF_GEMM_QUAD_TILE");
+    const char* env = rf::env_str("RF_GEMM_QUAD_TILE");
     if (!env) return 256256;
     int bm = 0, bn = 0;
     if (sscanf(env, "%dx%d", &bm, &bn) != 2) return 256256;
@@ -3729,8 +3755,7 @@ static int quad_tile() {
 }
 
 static int quad_mode(int m, int n, int k, int64_t lda, int64_t ldw, int epilogue) {
-    const char* env = getenv("RF_GEMM_QUAD");
-    const int mode = env ? atoi(env) : 0;
+    const int mode = rf::env_int("RF_GEMM_QUAD", 0);
     if (mode <= 0 || k % 128 || m <= 0) return 0;  // (the loop runs whole pairs of 64-deep K-tiles)
     const int t = quad_tile(), bn = t % 1000;
     if (bn != 256 && bn != 192 && bn != 128) return 0;
@@ -3747,8 +3772,7 @@ static int launch_quad(EngineArgs a, int mode, void* workspace, int64_t ws_bytes
     // RF_GEMM_QUAD_STG: 0 = LDS-DMA (default), 1 = register staging.  Measured (profiles/r4_quad_reg_study.txt):
     // staging a 64-deep K-tile through registers costs 64 VGPRs a lane at 256x256, which the 256 accumulator
     // AGPRs leave no room for; the loop spills and runs 2-3x slower than the DMA form.
-    const char* stg_env = getenv("RF_GEMM_QUAD_STG");
-    if (stg_env && atoi(stg_env) == 1) return launch_quad_s<WM, WN, EPI, NT, 1>(a, mode, workspace, ws_bytes, stream, what);
+    if (rf::env_int("RF_GEMM_QUAD_STG", 0) == 1) return launch_quad_s<WM, WN, EPI, NT, 1>(a, mode, workspace, ws_bytes, stream, what);
     return launch_quad_s<WM, WN, EPI, NT, 0>(a, mode, workspace, ws_bytes, stream, what);
 }
 
@@ -3772,12 +3796,9 @@ static int launch_quad_s(EngineArgs a, int mode, void* workspace, int64_t ws_byt
 template <int WM, int WN, int NT>
 static int run_quad_t(const EngineArgs& p, int epilogue, int mode, void* workspace, int64_t ws_bytes, void* stream,
                       const char* what) {
-    switch (epilogue) {
-        case RF_EPI_BF16: return launch_quad<WM, WN, E_BF16, NT>(p, mode, workspace, ws_bytes, stream, what);
-        case RF_EPI_F32: return launch_quad<WM, WN, E_F32, NT>(p, mode, workspace, ws_bytes, stream, what);
-        case RF_EPI_ADD_F32: return launch_quad<WM, WN, E_ADD, NT>(p, mode, workspace, ws_bytes, stream, what);
-        default: return launch_quad<WM, WN, E_SWIGLU, NT>(p, mode, workspace, ws_bytes, stream, what);
-    }
+    return with_epi(epilogue, [&](auto e) {
+        return launch_quad<WM, WN, decltype(e)::value, NT>(p, mode, workspace, ws_bytes, stream, what);
+    });
 }
 
 template <int NT>
@@ -3793,22 +3814,11 @@ static int run_quad(const EngineArgs& p, int epilogue, int mode, void* workspace
 }
 #endif  // RF_STUDY
 
-// the deferred-RMSNorm operands of one GEMM (rf_gemm_add_prenorm: xg / norm_g / ss_out; rf_gemm_rownorm: rs_*)
-struct NormIO {
-    void* xg = nullptr;
-    int64_t ldxg = 0;
-    const float* norm_g = nullptr;
-    float* ss_out = nullptr;
-    int xg_f16 = 0;
-    const float* rs_part = nullptr;
-    float rs_n = 0.f, rs_eps = 0.f;
-    float* seg_ss = nullptr;
-    int seg_w = 0, seg_n = 0;
-};
-
+// norm: the deferred-RMSNorm fields of EngineArgs, set by rf_gemm_add_prenorm (xg / norm_g / ss_out) or
+// rf_gemm_rownorm (rs_* / seg_*); every other field of the launch is filled here
 static int gemm_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, void* c, int64_t ldc,
                      const float* bias, int m, int n, int k, int epilogue, void* workspace, int64_t ws_bytes,
-                     void* stream, const int* gate, bool f16 = false, const NormIO* nio = nullptr) {
+                     void* stream, const int* gate, bool f16 = false, const EngineArgs* norm = nullptr) {
     RF_REQUIRE(a && w && c, "rf_gemm_bf16: null pointer");
     int out_f16 = 0;
     if (epilogue == RF_EPI_F16 || epilogue == RF_EPI_SWIGLU_F16) {  // fp16 16-bit outputs
@@ -3823,86 +3833,46 @@ static int gemm_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, voi
     RF_REQUIRE(epilogue >= RF_EPI_BF16 && epilogue <= RF_EPI_SWIGLU, "rf_gemm_bf16: bad epilogue %d", epilogue);
     RF_REQUIRE(ldc >= (epilogue == RF_EPI_SWIGLU ? n / 2 : n) && ldc % 4 == 0, "rf_gemm_bf16: ldc too small/unaligned");
     RF_REQUIRE(((uintptr_t)c & 7) == 0, "rf_gemm_bf16: output must be 8-B aligned");
-    EngineArgs p{};
-    p.a = (const bf16_t*)a;
-    p.lda = lda;
-    p.w = (const bf16_t*)w;
-    p.ldw = ldw;
-    p.m = m;
-    p.n = n;
-    p.k = k;
-    p.c = c;
-    p.ldc = ldc;
+    EngineArgs p = norm ? *norm : EngineArgs{};
+    dense_args(p, a, lda, w, ldw, m, n, k, c, ldc);
     p.bias = bias;
     p.gate = gate;
     p.out_f16 = out_f16;
-    p.range = out_f16 ? rf::range_word() : nullptr;
-    if (nio) {
-        p.xg = (bf16_t*)nio->xg;
-        p.ldxg = nio->ldxg;
-        p.norm_g = nio->norm_g;
-        p.ss_out = nio->ss_out;
-        p.xg_f16 = nio->xg_f16;
-        p.rs_part = nio->rs_part;
-        p.rs_n = nio->rs_n;
-        p.rs_eps = nio->rs_eps;
-        p.seg_ss = nio->seg_ss;
-        p.seg_w = nio->seg_w;
-        p.seg_n = nio->seg_n;
-        if (nio->xg && nio->xg_f16) p.range = rf::range_word();
-    }
+    p.range = (out_f16 || (p.xg && p.xg_f16)) ? rf::range_word() : nullptr;
+    const char* what = f16 ? "rf_gemm_f16" : "rf_gemm_bf16";
+    const bool ws_ok = workspace && ws_bytes >= SK_WS_BYTES;
 #ifdef RF_STUDY
-    if (const int qm = nio ? 0 : quad_mode(m, n, k, lda, ldw, epilogue)) {  // (the 4-wave epilogue has no norm I/O)
-        return f16 ? run_quad<P_F16>(p, epilogue, qm, workspace, ws_bytes, stream, "rf_gemm_f16")
-                   : run_quad<1>(p, epilogue, qm, workspace, ws_bytes, stream, "rf_gemm_bf16");
+    if (const int qm = norm ? 0 : quad_mode(m, n, k, lda, ldw, epilogue)) {  // (the 4-wave epilogue has no norm I/O)
+        return f16 ? run_quad<P_F16>(p, epilogue, qm, workspace, ws_bytes, stream, what)
+                   : run_quad<1>(p, epilogue, qm, workspace, ws_bytes, stream, what);
     }
 #else
-    if (getenv("RF_GEMM_QUAD") && atoi(getenv("RF_GEMM_QUAD")) > 0) return rf::study_only("rf_gemm: RF_GEMM_QUAD");
+    if (rf::env_int("RF_GEMM_QUAD", 0) > 0) return rf::study_only("rf_gemm: RF_GEMM_QUAD");
 #endif
-    if (workspace && ws_bytes >= SK_WS_BYTES && skph(m, n, k)) {
+    if (ws_ok && skph(m, n, k)) {
         if (const int rc = sk_setup(p, workspace, stream)) return rc;
         const int64_t tiles = (int64_t)((m + 255) / 256) * (n / 256);
         p.persist = tiles % 256 == 0 && persist_on();  // whole tiles per block either way: prefetching form
-        if (f16) {
-            switch (epilogue) {
-                case RF_EPI_BF16: return launch_phased_sk<E_BF16, P_F16>(p, 256, stream, "rf_gemm_f16");
-                case RF_EPI_F32: return launch_phased_sk<E_F32, P_F16>(p, 256, stream, "rf_gemm_f16");
-                case RF_EPI_ADD_F32: return launch_phased_sk<E_ADD, P_F16>(p, 256, stream, "rf_gemm_f16");
-                default: return launch_phased_sk<E_SWIGLU, P_F16>(p, 256, stream, "rf_gemm_f16");
-            }
-        }
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_phased_sk<E_BF16>(p, 256, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_phased_sk<E_F32>(p, 256, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_phased_sk<E_ADD>(p, 256, stream, "rf_gemm_bf16");
-            default: return launch_phased_sk<E_SWIGLU>(p, 256, stream, "rf_gemm_bf16");
-        }
+        return with_epi(epilogue, [&](auto e) {
+            return f16 ? launch_phased_sk<decltype(e)::value, P_F16>(p, 256, stream, what)
+                       : launch_phased_sk<decltype(e)::value>(p, 256, stream, what);
+        });
     }
     const int cfg = pick_cfg(m, n, k, epilogue);
-    if (f16) return run_dp_f16(cfg, p, epilogue, stream);
-    const bool big = cfg != 128;
-    const int grid = (!big && workspace && ws_bytes >= SK_WS_BYTES) ? sk_grid(m, n, k) : 0;
+    if (f16) return run_dp<P_F16>(TileTable{}, cfg, p, epilogue, stream);
+    const bool big = cfg != TC_R128;
+    const int grid = (!big && ws_ok) ? sk_grid(m, n, k) : 0;
     if (grid) {
         if (const int rc = sk_setup(p, workspace, stream)) return rc;
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_sk<T128, E_BF16>(p, grid, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_sk<T128, E_F32>(p, grid, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_sk<T128, E_ADD>(p, grid, stream, "rf_gemm_bf16");
-            default: return launch_sk<T128, E_SWIGLU>(p, grid, stream, "rf_gemm_bf16");
-        }
+        return with_epi(epilogue, [&](auto e) { return launch_sk<T128, decltype(e)::value>(p, grid, stream, what); });
     }
     // 256x256 tiles at one 512-thread block per CU reach ~1.2 PF/s when every CU has work; when the tile count
     // would leave a ragged last round, stream-K the K loop over exactly 256 blocks instead.
-    if (workspace && ws_bytes >= SK_WS_BYTES && n % 256 == 0 && sk256(m, n, k)) {
+    if (ws_ok && n % 256 == 0 && sk256(m, n, k)) {
         if (const int rc = sk_setup(p, workspace, stream)) return rc;
-        switch (epilogue) {
-            case RF_EPI_BF16: return launch_sk<T256, E_BF16>(p, 256, stream, "rf_gemm_bf16");
-            case RF_EPI_F32: return launch_sk<T256, E_F32>(p, 256, stream, "rf_gemm_bf16");
-            case RF_EPI_ADD_F32: return launch_sk<T256, E_ADD>(p, 256, stream, "rf_gemm_bf16");
-            default: return launch_sk<T256, E_SWIGLU>(p, 256, stream, "rf_gemm_bf16");
-        }
+        return with_epi(epilogue, [&](auto e) { return launch_sk<T256, decltype(e)::value>(p, 256, stream, what); });
     }
-    return run_dp(cfg, p, epilogue, stream);
+    return run_dp<1>(TileTable{}, cfg, p, epilogue, stream);
 }
 
 extern "C" int rf_gemm_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, void* c, int64_t ldc,
@@ -3934,8 +3904,8 @@ extern "C" int rf_gemm_add_prenorm(const void* a, int64_t lda, const void* w, in
         if (rc != RF_OK) return rc;
         return rf_prenorm(x, ldx, norm_w, xg, ldxg, ss, m, n, operand_dtype, stream);
     }
-    NormIO nio;
-    nio.xg = xg;
+    EngineArgs nio{};
+    nio.xg = (bf16_t*)xg;
     nio.ldxg = ldxg;
     nio.norm_g = norm_w;
     nio.ss_out = ss;
@@ -3960,7 +3930,7 @@ extern "C" int rf_gemm_rownorm(const void* a, int64_t lda, const void* w, int64_
                            (int64_t)seg_w * n_seg <= n),
                "rf_gemm_rownorm: seg_ss needs a 16-bit (non-SwiGLU) epilogue, 16-B alignment, seg_w %% 256 == 0 and "
                "<= %d, n_seg >= 1 segments inside N", PN_SLOTS * 128);
-    NormIO nio;
+    EngineArgs nio{};
     nio.rs_part = ss;
     nio.rs_n = (float)norm_dim;
     nio.rs_eps = eps;
@@ -4001,15 +3971,7 @@ extern "C" int rf_gemm_qk_rope(const void* a, int64_t lda, const void* w, int64_
     RF_REQUIRE(!pos || (freqs && n_freqs > 0 && 9 * n_freqs <= 64 && ld_pos >= 9 && pos_div >= 1),
                "rf_gemm_qk_rope: pos needs freqs with 9 * n_freqs <= 64, ld_pos >= 9 and pos_div >= 1");
     EngineArgs p{};
-    p.a = (const bf16_t*)a;
-    p.lda = lda;
-    p.w = (const bf16_t*)w;
-    p.ldw = ldw;
-    p.m = m;
-    p.n = n;
-    p.k = k;
-    p.c = c;
-    p.ldc = ldc;
+    dense_args(p, a, lda, w, ldw, m, n, k, c, ldc);
     p.rs_part = ss;
     p.rs_n = (float)norm_dim;
     p.rs_eps = eps;
@@ -4025,7 +3987,7 @@ extern "C" int rf_gemm_qk_rope(const void* a, int64_t lda, const void* w, int64_
     p.rope_qscale = q_scale;
     const bool f16 = operand_dtype == RF_DT_F16;
     const int cfg = pick_cfg(m, n, k, RF_EPI_BF16);
-    const bool t96 = n % 256 == 0 && (cfg == 962 || cfg != 12884);
+    const bool t96 = n % 256 == 0 && cfg != TC_R128w8k2;  // (K % 64 == 0 is required above)
     if (t96) return f16 ? launch_rope<T96x256, P_F16>(p, stream) : launch_rope<T96x256, 1>(p, stream);
     return f16 ? launch_rope<T128w8k2s4, P_F16>(p, stream) : launch_rope<T128w8k2s4, 1>(p, stream);
 }
@@ -4051,46 +4013,31 @@ extern "C" int rf_gemm_mx8(const void* a, int64_t lda, const void* sa, int64_t l
     RF_REQUIRE(epilogue >= RF_EPI_BF16 && epilogue <= RF_EPI_SWIGLU, "rf_gemm_mx8: bad epilogue %d", epilogue);
     RF_REQUIRE(ldc >= (epilogue == RF_EPI_SWIGLU ? n / 2 : n) && ldc % 4 == 0, "rf_gemm_mx8: ldc too small/unaligned");
     EngineArgs p{};
-    p.a = (const bf16_t*)a;
-    p.lda = lda;
-    p.w = (const bf16_t*)w;
-    p.ldw = ldw;
+    dense_args(p, a, lda, w, ldw, m, n, k, c, ldc);
     p.sa = (const uint8_t*)sa;
     p.sw = (const uint8_t*)sw;
     p.ld_sa = (int)ld_sa;
     p.ld_sw = (int)ld_sw;
-    p.m = m;
-    p.n = n;
-    p.k = k;
-    p.c = c;
-    p.ldc = ldc;
     p.bias = bias;
     hipStream_t st = (hipStream_t)stream;
-    static const bool plain = getenv("RF_MX8_PLAIN") && atoi(getenv("RF_MX8_PLAIN")) != 0;  // A/B: the unstaggered loop
-    if (!plain) {
+    if (RF_ENV_ONCE("RF_MX8_PLAIN", 0) == 0) {  // (1: the unstaggered loop, A/B)
         const int tiles_m = (m + 127) / 128, tiles_n = n / 256;
         const int nwg = tiles_m * tiles_n;
         p.group_m = pick_group_m(tiles_m, tiles_n, 128, 256, (nwg + 7) / 8, (int64_t)m * k);
         const dim3 g(nwg), b(512);
-        switch (epilogue) {
-            case RF_EPI_BF16: RF_LAUNCH((mx8_p3_kernel<E_BF16>), g, b, 0, st, p); break;
-            case RF_EPI_F32: RF_LAUNCH((mx8_p3_kernel<E_F32>), g, b, 0, st, p); break;
-            case RF_EPI_ADD_F32: RF_LAUNCH((mx8_p3_kernel<E_ADD>), g, b, 0, st, p); break;
-            default: RF_LAUNCH((mx8_p3_kernel<E_SWIGLU>), g, b, 0, st, p); break;
-        }
-        return rf::check_launch("rf_gemm_mx8");
+        return with_epi(epilogue, [&](auto e) {
+            RF_LAUNCH((mx8_p3_kernel<decltype(e)::value>), g, b, 0, st, p);
+            return rf::check_launch("rf_gemm_mx8");
+        });
     }
     const int tiles_m = (m + 255) / 256, tiles_n = n / 256;
     const int nwg = tiles_m * tiles_n;
     p.group_m = pick_group_m(tiles_m, tiles_n, 256, 256, (nwg + 7) / 8, (int64_t)m * k);
     const dim3 g(nwg), b(512);
-    switch (epilogue) {
-        case RF_EPI_BF16: RF_LAUNCH((mx8_kernel<E_BF16>), g, b, 0, st, p); break;
-        case RF_EPI_F32: RF_LAUNCH((mx8_kernel<E_F32>), g, b, 0, st, p); break;
-        case RF_EPI_ADD_F32: RF_LAUNCH((mx8_kernel<E_ADD>), g, b, 0, st, p); break;
-        default: RF_LAUNCH((mx8_kernel<E_SWIGLU>), g, b, 0, st, p); break;
-    }
-    return rf::check_launch("rf_gemm_mx8");
+    return with_epi(epilogue, [&](auto e) {
+        RF_LAUNCH((mx8_kernel<decltype(e)::value>), g, b, 0, st, p);
+        return rf::check_launch("rf_gemm_mx8");
+    });
 }
 
 extern "C" int rf_quant_mx8(const void* x, int64_t ldx, int rows, int cols, void* q, int64_t ldq, void* scales,
@@ -4109,22 +4056,21 @@ extern "C" int rf_quant_mx8(const void* x, int64_t ldx, int rows, int cols, void
 // output channels (or 64: output_conv2) when they make at least one block per CU (RF_CONV_HALO2=0: never,
 // 1: whenever it can)
 static bool halo2_ok(const EngineArgs& a) {
-    const char* env = getenv("RF_CONV_HALO2");
-    if (env && atoi(env) == 0) return false;
-    if (!env && getenv("RF_CONV_TILE")) return false;  // an explicit tile choice (A/B, tests) keeps its kernel
+    const int env = rf::env_int("RF_CONV_HALO2", -1);  // (-1: unset)
+    if (env == 0) return false;
+    if (!rf::env_set("RF_CONV_HALO2") && rf::env_set("RF_CONV_TILE")) return false;  // an explicit tile choice (A/B, tests) keeps its kernel
     if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
     if (a.cin_pad % 32 || (a.n % 128 && a.n != 64) || a.ho % h2::TH || a.wo % h2::TW || a.m % 512) return false;
     const int64_t blocks = (int64_t)(a.m / 512) * (a.n == 64 ? 1 : a.n / 128);
-    return (env && atoi(env) == 1) || blocks >= 256;
+    return env == 1 || blocks >= 256;
 }
 
 static int launch_halo2(EngineArgs a, void* stream, const char* what) {
     const bool n64 = a.n == 64;
     const int nwg = (a.m / 512) * (n64 ? 1 : a.n / 128);
-    const char* env = getenv("RF_CONV_H2S");  // W ring depth (slices in flight + 1): 4 (default), 3 or 5
-    const int ring = env ? atoi(env) : 4;
+    const int ring = rf::env_int("RF_CONV_H2S", 4);  // W ring depth (slices in flight + 1): 4 (default), 3 or 5
     const hipStream_t st = (hipStream_t)stream;
-    const int dbg = getenv("RF_H2_DBG") ? atoi(getenv("RF_H2_DBG")) : 0;  // ablation timing only
+    const int dbg = rf::env_int("RF_H2_DBG", 0);  // ablation timing only
 #ifndef RF_STUDY
     if (dbg) return rf::study_only("rf_conv: RF_H2_DBG (halo2 ablation builds)");
 #else
@@ -4152,15 +4098,14 @@ static int launch_halo2(EngineArgs a, void* stream, const char* what) {
 // halo3_kernel serves halo2's non-final convolutions with a multiple of 128 output channels (RF_CONV_HALO3=0:
 // halo2 instead); the bank must be addressable by 32-bit buffer offsets
 static bool halo3_ok(const EngineArgs& a) {
-    const char* env = getenv("RF_CONV_HALO3");
-    if ((env && atoi(env) == 0) || (a.flags & RF_CONV_FINAL) || a.n % 128 || a.deconv) return false;
+    if (rf::env_int("RF_CONV_HALO3", 1) == 0 || (a.flags & RF_CONV_FINAL) || a.n % 128 || a.deconv) return false;
     if ((int64_t)128 * a.ldw * 2 >= 0x7fffffff) return false;
     return halo2_ok(a);
 }
 
 static int launch_halo3(EngineArgs a, void* stream, const char* what) {
     const int nwg = (a.m / 512) * (a.n / 128);
-    const int dbg = getenv("RF_H3_DBG") ? atoi(getenv("RF_H3_DBG")) : 0;  // ablation timing only
+    const int dbg = rf::env_int("RF_H3_DBG", 0);  // ablation timing only
 #ifndef RF_STUDY
     if (dbg) return rf::study_only("rf_conv: RF_H3_DBG (halo3 ablation builds, garbage results)");
     RF_LAUNCH(halo3_kernel<0>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
@@ -4185,8 +4130,7 @@ static int launch_halo3(EngineArgs a, void* stream, const char* what) {
 // conv3x3_c32_kernel serves the fused-head 3x3 convolution with <= 32 filters (output_conv2) on whole 16 x 32
 // tiles (RF_CONV_C32=0: the halo2 / engine paths instead)
 static bool c32_ok(const EngineArgs& a) {
-    const char* env = getenv("RF_CONV_C32");
-    if ((env && atoi(env) == 0) || !(a.flags & RF_CONV_FINAL) || a.cout > 32 || a.n < 32) return false;
+    if (rf::env_int("RF_CONV_C32", 1) == 0 || !(a.flags & RF_CONV_FINAL) || a.cout > 32 || a.n < 32) return false;
     if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
     return a.cin_pad % 32 == 0 && a.ho % c32::TH == 0 && a.wo % c32::TW == 0 && a.m > 0 && a.n_fin <= c32::NFIN;
 }
@@ -4201,14 +4145,14 @@ static int launch_c32(EngineArgs a, void* stream, const char* what) {
 // multiple of 64 output channels and at least one block per CU (RF_CONV_HK=0: the halo2 / engine paths; 1: whenever
 // it can)
 static bool hk_ok(const EngineArgs& a) {
-    const char* env = getenv("RF_CONV_HK");
-    if (!env || atoi(env) == 0 || (a.flags & RF_CONV_FINAL) || a.deconv) return false;  // opt-in: see DESIGN §3.4
+    const int env = rf::env_int("RF_CONV_HK", 0);
+    if (env == 0 || (a.flags & RF_CONV_FINAL) || a.deconv) return false;  // opt-in: see DESIGN §3.4
 #ifndef RF_STUDY
     return true;  // (the production build refuses it in launch_hk)
 #else
     if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
     if (a.cin_pad % 32 || a.n % hk::NCO || a.ho % hk::TH || a.wo % hk::TW || a.m <= 0) return false;
-    return atoi(env) == 1 || (int64_t)(a.m / (hk::TH * hk::TW)) * (a.n / hk::NCO) >= 256;
+    return env == 1 || (int64_t)(a.m / (hk::TH * hk::TW)) * (a.n / hk::NCO) >= 256;
 #endif
 }
 
@@ -4223,6 +4167,20 @@ static int launch_hk(EngineArgs a, void* stream, const char* what) {
 #endif
 }
 
+// Conv tile codes: what RF_CONV_TILE=<number> forces (tests and tools/kbench.py pass these numbers); unset = CT_AUTO,
+// the heuristics of conv_common / conv_f16_dp.  Unrelated to the dense GEMM's RF_GEMM_TILE codes.
+enum ConvTile : int {
+    CT_AUTO = 0,
+    CT_64 = 64,          // 64x64 (T64c), data-parallel
+    CT_128 = 128,        // 128x128, 4 waves (fp16: the halo kernel when it serves the shape)
+    CT_256 = 256,        // fp16: 256x256 when N % 256 == 0; bf16x3: 256x128
+    CT_128w8 = 1288,     // fp16: 128x128, 8 waves
+    CT_256x128 = 2561,   // fp16: 256x128, 8 waves
+    CT_64x128 = 6412,    // fp16: 64x128 (T64x128c)
+    CT_64SK = 6464,      // fp16: 64x64, stream-K when the grid allows (conv_common), else data-parallel
+};
+static int conv_tile_env() { return rf::env_int("RF_CONV_TILE", CT_AUTO); }
+
 // fp16 convolutions (one MFMA per product): the 256x256 tile when the filter bank is a multiple of 256
 // wide and there is >= one tile per CU (the im2col gather of A is then read once per pixel tile),
 // 256x64 for <= 64 output channels, else 128x128 (faster than 256x128 on every DPT shape measured)
@@ -4232,24 +4190,23 @@ static int conv_f16_dp(EngineArgs& p, void* stream, const char* what, int tile =
     if (GATHER && hk_ok(p)) return launch_hk(p, stream, what);
     if (GATHER && halo3_ok(p)) return launch_halo3(p, stream, what);
     if (GATHER && halo2_ok(p)) return launch_halo2(p, stream, what);
-    const char* env = getenv("RF_CONV_TILE");
-    const int t = tile ? tile : env ? atoi(env) : 0;
+    const int t = tile ? tile : conv_tile_env();
     // (RF_CONV_HALO=1 runs it halo-tiled: 90 -> 140 us at 512^2, 128 -> 32; a 128x64 tile at two blocks per
     // CU measured the same 90 us with or without the halo, so the gathered 256x64 launch stays the default)
     if (p.n == 64) return launch_conv<T256x64, P_F16, GATHER>(p, stream, what);
-    if (t == 64 || t == 6464) return launch_conv<T64c, P_F16, GATHER>(p, stream, what);
-    if (t == 6412) return launch_conv<T64x128c, P_F16, GATHER>(p, stream, what);
-    if (t == 128) return launch_conv<T128, P_F16, GATHER>(p, stream, what);
-    if (t == 1288) return launch_conv<T128w8, P_F16, GATHER>(p, stream, what);
-    if (p.n % 256 == 0 && (t == 256 || (!t && ((p.m + 255) / 256) * (p.n / 256) >= 256)))
-        return (getenv("RF_CONV_PHASED") && atoi(getenv("RF_CONV_PHASED")) && use_phased(p.n, p.k))
+    if (t == CT_64 || t == CT_64SK) return launch_conv<T64c, P_F16, GATHER>(p, stream, what);
+    if (t == CT_64x128) return launch_conv<T64x128c, P_F16, GATHER>(p, stream, what);
+    if (t == CT_128) return launch_conv<T128, P_F16, GATHER>(p, stream, what);
+    if (t == CT_128w8) return launch_conv<T128w8, P_F16, GATHER>(p, stream, what);
+    if (t == CT_256x128) return launch<T256x128, E_CONV, P_F16, GATHER>(p, stream, what);  // (never the halo kernel)
+    if (p.n % 256 == 0 && (t == CT_256 || (t == CT_AUTO && ((p.m + 255) / 256) * (p.n / 256) >= 256)))
+        return (rf::env_int("RF_CONV_PHASED", 0) != 0 && use_phased(p.n, p.k))
                    ? launch_phased<E_CONV, P_F16, GATHER, 256>(p, stream, what)
                    : launch_conv<T256, P_F16, GATHER>(p, stream, what);
-    if (t == 2561) return launch<T256x128, E_CONV, P_F16, GATHER>(p, stream, what);
     // up to two 128x128 tiles per CU: the 8-wave tile (two waves per SIMD) hides the gathered staging's
     // latency (128^2 DPT level: 52 -> 41 us); with more tiles the 4-wave tile's extra blocks do that
     const int64_t tiles = (int64_t)((p.m + 127) / 128) * (p.n / 128);
-    if (t != 128 && tiles <= 512) return launch_conv<T128w8, P_F16, GATHER>(p, stream, what);
+    if (tiles <= 512) return launch_conv<T128w8, P_F16, GATHER>(p, stream, what);
     return launch_conv<T128, P_F16, GATHER>(p, stream, what);
 }
 
@@ -4263,7 +4220,7 @@ static int conv_dispatch(EngineArgs& p, bool gather, bool big, int64_t sk_grid_n
     if (sk_grid_n) {
         if (const int rc = sk_setup(p, workspace, stream)) return rc;
         // fp16 convolutions stream-K over the 8-wave 128x128 tile (64^2 / 32^2 DPT levels: 1.6x / 2.1x)
-        if (NT == P_F16 && !(getenv("RF_CONV_SKW8") && atoi(getenv("RF_CONV_SKW8")) == 0))
+        if (NT == P_F16 && rf::env_int("RF_CONV_SKW8", 1) != 0)
             return gather ? launch_sk<T128w8, E_CONV, NT, true>(p, (int)sk_grid_n, stream, what)
                           : launch_sk<T128w8, E_CONV, NT, false>(p, (int)sk_grid_n, stream, what);
         return gather ? launch_sk<T128, E_CONV, NT, true>(p, (int)sk_grid_n, stream, what)
@@ -4318,22 +4275,19 @@ static int conv_common(EngineArgs& p, int nterm, bool gather, const void* w_hi, 
     if (p.m <= 0) return RF_OK;
     // 256x128 (8 waves) halves the L2 traffic per FLOP of the 128x128 tile but runs one block per CU:
     // use it only when it still yields >= one tile per CU.
-    const char* env = getenv("RF_CONV_TILE");
-    const bool big = env ? atoi(env) == 256 : ((p.m + 255) / 256) * (p.n / 128) >= 256;
+    const bool big = rf::env_set("RF_CONV_TILE") ? conv_tile_env() == CT_256 : ((p.m + 255) / 256) * (p.n / 128) >= 256;
     // Too few 128x128 tiles for 256 CUs (one bf16x3 block per CU): stream-K over the K loop, each block
     // keeping >= 8 K-steps.
-    const char* sk_env = getenv("RF_CONV_SK");
     int64_t skg = 0;
-    int ct = env ? atoi(env) : 0;
+    int ct = conv_tile_env();
     // small DPT levels (<= 4,096 output pixels per launch: the 64^2 / 32^2 refinenets and their rn convs): the
     // 64x64 tile, data-parallel at K <= 2,304 and stream-K above (GPU time per launch, rocprofv3 over
     // tools/kbench.py conv: 256->256 @32 32.4 -> 26.6 us, @64 30.1 -> 27.6 us, 1024->256 @32 50.4 -> 41.4 us;
     // 1024->256 @64 stays on the default, 54.4 vs 68.1 us).  RF_CONV_SMALL=0 keeps the default tiles.
-    static const bool small_on = !getenv("RF_CONV_SMALL") || atoi(getenv("RF_CONV_SMALL")) != 0;
-    if (!ct && small_on && nterm == P_F16 && gather && p.kw == 3 && p.n % 64 == 0 && p.m <= 4096 &&
+    if (!ct && RF_ENV_ONCE("RF_CONV_SMALL", 1) != 0 && nterm == P_F16 && gather && p.kw == 3 && p.n % 64 == 0 && p.m <= 4096 &&
         (p.k <= 2304 || p.m <= 1024))
-        ct = p.k <= 2304 ? 64 : 6464;
-    if (nterm == P_F16 && ct == 6464 && p.n % 64 == 0 && workspace && ws_bytes >= SK_WS_BYTES) {
+        ct = p.k <= 2304 ? CT_64 : CT_64SK;
+    if (nterm == P_F16 && ct == CT_64SK && p.n % 64 == 0 && workspace && ws_bytes >= SK_WS_BYTES) {
         // A/B: stream-K over the 64x64 small-level tile, up to two blocks per CU, >= 12 K-steps per block
         const int64_t tiles = (int64_t)((p.m + 63) / 64) * (p.n / 64);
         const int64_t grid = std::min<int64_t>(512, tiles * (p.k / BK) / 12);
@@ -4343,14 +4297,14 @@ static int conv_common(EngineArgs& p, int nterm, bool gather, const void* w_hi, 
                           : launch_sk<T64c, E_CONV, P_F16, false>(p, (int)grid, stream, what);
         }
     }
-    if (!big && p.n % 128 == 0 && workspace && ws_bytes >= SK_WS_BYTES && !(sk_env && atoi(sk_env) == 0) &&
-        !(nterm == P_F16 && (ct == 64 || ct == 6412 || ct == 6464))) {
+    if (!big && p.n % 128 == 0 && workspace && ws_bytes >= SK_WS_BYTES && rf::env_int("RF_CONV_SK", 1) != 0 &&
+        !(nterm == P_F16 && (ct == CT_64 || ct == CT_64x128 || ct == CT_64SK))) {
         const int64_t tiles = (int64_t)((p.m + 127) / 128) * (p.n / 128);
         const int64_t work = tiles * (p.k / BK);
         const int64_t grid = std::min<int64_t>(256, work / 8);
         if (tiles < 192 && grid > tiles) skg = grid;
     }
-    return nterm == P_F16 ? conv_dispatch<P_F16>(p, gather, big, skg, workspace, stream, what, ct == 64 ? 64 : 0)
+    return nterm == P_F16 ? conv_dispatch<P_F16>(p, gather, big, skg, workspace, stream, what, ct == CT_64 ? CT_64 : CT_AUTO)
                           : conv_dispatch<3>(p, gather, big, skg, workspace, stream, what);
 }
 
@@ -4531,8 +4485,7 @@ extern "C" int rf_conv1x1_f16_group(int n_conv, const void* const* in, const int
         d[q].p_ld = p_ld[q];
     }
     // (RF_CONV_GROUP_DENSE=0: the gathered 32-deep loop, A/B)
-    static const bool dense = !getenv("RF_CONV_GROUP_DENSE") || atoi(getenv("RF_CONV_GROUP_DENSE")) != 0;
-    bool ok = dense;
+    bool ok = RF_ENV_ONCE("RF_CONV_GROUP_DENSE", 1) != 0;
     for (int q = 0; q < n_conv; ++q) ok = ok && cin_pad[q] % 64 == 0;
     return ok ? conv_group_launch<true>(n_conv, d, stream, "rf_conv1x1_f16_group")
               : conv_group_launch<false>(n_conv, d, stream, "rf_conv1x1_f16_group");

@@ -131,6 +131,51 @@ def test_gemm_256_tiles(monkeypatch, tile, m, n, k):
     assert relerr(outs.float(), refs) < 5e-3
 
 
+def _tile_codes():
+    """Every RF_GEMM_TILE code of the dispatch table: the enumerators of `enum TileCode` in csrc/gemm.hip."""
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "renderformer_amd", "csrc",
+                       "gemm.hip")
+    with open(src) as f:
+        body = re.search(r"enum TileCode[^{]*\{(.*?)\};", f.read(), re.S).group(1)
+    codes = sorted(int(v) for v in re.findall(r"\bTC_\w+\s*=\s*(\d+)", body))
+    assert len(codes) == len(set(codes)) >= 25, codes
+    return codes
+
+
+TABLE_SHAPES = [(1, 256, 64), (300, 384, 96)]  # the second: N % 256 != 0 and K % 64 != 0 (every fall-through)
+
+
+@pytest.fixture(scope="module")
+def table_cases():
+    """Operands and fp64 products of TABLE_SHAPES for both operand types, computed once."""
+    cases = []
+    for m, n, k in TABLE_SHAPES:
+        g = torch.Generator(device="cpu").manual_seed(m + 11 * n + k)
+        a32 = torch.randn(m, k, generator=g)
+        w32 = torch.randn(n, k, generator=g) / math.sqrt(k)
+        for dt in (torch.bfloat16, torch.float16):
+            a, w = a32.to(dt).to(dev), w32.to(dt).to(dev)
+            cases.append((a, w, a.double() @ w.double().t()))
+    return cases
+
+
+# every code of the table, one number that is not in it, and 256 without the phased loop (the ring's 256x256)
+@pytest.mark.parametrize("code,phased", [(c, "1") for c in _tile_codes()] + [(777, "1"), (256, "0")])
+def test_gemm_tile_table(monkeypatch, table_cases, code, phased):
+    """The tile table of the dense dispatch: every RF_GEMM_TILE code (also those nothing selects by default, and a
+    number outside the table) on bf16 and fp16 operands, on a shape that meets every precondition and one that
+    fails N % 256 and K % 64 (the fall-through to the 128x128 ring), fp32 epilogue vs fp64."""
+    ops = _ops()
+    monkeypatch.setenv("RF_GEMM_TILE", str(code))
+    monkeypatch.setenv("RF_GEMM_PHASED", phased)
+    for a, w, ref in table_cases:
+        out = torch.empty(a.shape[0], w.shape[0], device=dev)
+        ops.gemm(a, w, out, None, ops.EPI_F32)
+        assert relerr(out, ref) < 1e-5, (code, tuple(a.shape), a.dtype)
+
+
 F16_TILES = {"auto": None, "256ph": "256", "128x256ph": "1282", "96x256ph3": "964", "64x256ph3": "645",
              "128x256ph3": "1283", "96x256ring": "962", "128ring8wk64": "12884", "128ring": "128", "skph": "skph",
              "quad": "quad1", "quadsk": "quad2", "quad128x192": "quad1@128x192", "quad160x256sk": "quad2@160x256",
