@@ -48,6 +48,14 @@
  *                      whose weights hold the folded 1x1 out_conv (dpt.py:157-159, 268-271; RF_CONV_BORDER_BIAS)
  *   rf_encoder_forward TransformerEncoder.forward (attention.py:579-590): the whole stage-1 stack in one call
  *   rf_decoder_forward TransformerDecoder.forward (attention.py:673-688) + the DPT taps (view_transformer.py:85)
+ *   rf_scene_kv        the camera-independent head of TransformerDecoder.forward: kv_norm + k_proj / v_proj of every
+ *                      layer (attention.py:508, 121-125) on the stage-1 output, once per scene.  The caller keeps
+ *                      the result and hands it to rf_decoder_forward (rf_decoder_desc.kv_all) for every camera that
+ *                      follows: such a call skips the context norm and the K/V GEMM and launches exactly what a full
+ *                      call launches after them, on the same bits.  The kept state of a scene is the stage-1 output
+ *                      [T1, D] f32 plus kv_all [T1, n_layers * 2 * Dv] bf16: T1 * (4 * D + n_layers * 4 * Dv) bytes.
+ *                      kv_all depends on the operand type: after an fp16 overflow fallback (the model moves to bf16
+ *                      operands) it must be computed again with the bf16 weights.
  */
 #ifndef RF_H
 #define RF_H
@@ -64,6 +72,8 @@ extern "C" {
 #define RF_ERR_UNSUPPORTED 3
 #define RF_ERR_DEVICE 4       /* an earlier launch reported a device-side error (see rf_device_error) */
 
+/* Still 16 with rf_scene_kv and rf_decoder_desc.kv_all / ld_kv_all: a new symbol and two trailing descriptor fields
+ * that a zero-initialised caller leaves NULL / 0 (= the behaviour before them); nothing that existed changed. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -606,12 +616,27 @@ typedef struct {
                                                    k_norm_all in rf_gemm_qk_rope's pair-interleaved order: the query
                                                    rotation runs in the projection's epilogue (rf_gemm_qk_rope), the
                                                    keys' in rf_qk_norm_rope_groups_ilv, q's 1 / rms in rf_attn_fwd_qn */
+    /* K/V of every layer computed earlier by rf_scene_kv (bf16 [ctx_rows, ld_kv_all], layer i's K at column 2*D*i,
+       its V at 2*D*i + D; ld_kv_all >= n_layers * 2 * dim), or NULL.  When set, the context norm and the K/V GEMM
+       are skipped and K/V are read from here: ctx_norm and w_kv_all may be NULL, k_batch is allowed, ctx must still
+       be non-NULL but is not read, and the workspace holds no context operand and no K/V region. */
+    const void* kv_all;
+    int64_t ld_kv_all;
 } rf_decoder_desc;
 
 /* x[rows, dim] (f32 ray-token residual stream) through the decoder stack in place; the DPT taps are written as
  * they are produced.  Replaces TransformerDecoder.forward (attention.py:673-688) on packed rows. */
 int rf_decoder_forward(float* x, int64_t ldx, const rf_decoder_desc* desc, void* stream);
 int64_t rf_decoder_workspace_bytes(const rf_decoder_desc* desc);
+
+/* kv_all[ctx_rows, width] (bf16, row stride ld_kv_all >= width) = rmsnorm(ctx; ctx_norm) w_kv_all^T: the two launches
+ * rf_decoder_forward issues first when w_kv_all != NULL (rf_rmsnorm / rf_rmsnorm_f16 of ctx[ctx_rows, ctx_dim] into
+ * `scratch`, then rf_gemm_bf16 / rf_gemm_f16 with RF_EPI_BF16), with the same arguments, so kv_all holds the bits of
+ * the decoder's internal buffer.  width = n_layers * 2 * dim (a multiple of 128), ctx_dim % 64 == 0, w_kv_all
+ * [width, ctx_dim] and scratch (ctx_rows * ctx_dim * 2 bytes, 256-B aligned, caller-owned) in operand_dtype. */
+int rf_scene_kv(const float* ctx, int64_t ld_ctx, int ctx_rows, int ctx_dim, const float* ctx_norm,
+                const void* w_kv_all, int width, int operand_dtype, float eps, void* scratch, void* kv_all,
+                int64_t ld_kv_all, void* gemm_ws, int64_t gemm_ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,13 +7,16 @@ eager-PyTorch fallback for the compute path.
 """
 from .config import RenderFormerConfig
 
-__all__ = ["RenderFormerRenderingPipeline", "RenderFormer", "RenderFormerConfig"]
+__all__ = ["RenderFormerRenderingPipeline", "RenderFormer", "RenderFormerConfig", "EncodedScene"]
 
 
 def __getattr__(name):
     if name == "RenderFormer":
         from .model import RenderFormer
         return RenderFormer
+    if name == "EncodedScene":
+        from .model import EncodedScene
+        return EncodedScene
     if name == "RenderFormerRenderingPipeline":
         from .pipeline import RenderFormerRenderingPipeline
         return RenderFormerRenderingPipeline

@@ -103,6 +103,7 @@ SIGNATURES = {
     "rf_ktimer_read": [_P, _I],
     "rf_encoder_forward": [_P, _L, _P, _P],
     "rf_decoder_forward": [_P, _L, _P, _P],
+    "rf_scene_kv": [_P, _L, _I, _I, _P, _P, _I, _I, _F, _P, _P, _L, _P, _L, _P],
 }
 RF_ERR_DEVICE = 4
 
@@ -146,7 +147,7 @@ class DecoderDesc(ctypes.Structure):
                 ("n_cross", _I), ("cross_bounds", _P), ("cross_grid", _I), ("swin", _I), ("n_images", _I),
                 ("grid_h", _I), ("grid_w", _I), ("window", _I), ("shift", _I), ("self_problems", _P), ("n_self", _I),
                 ("taps", _P), ("n_taps", _I), ("workspace", _P), ("gemm_ws", _P), ("gemm_ws_bytes", _L),
-                ("attn_ws", _P), ("timer_cross", _I), ("qk_fused", _I)]
+                ("attn_ws", _P), ("timer_cross", _I), ("qk_fused", _I), ("kv_all", _P), ("ld_kv_all", _L)]
 
 
 class HipLibraryError(RuntimeError):

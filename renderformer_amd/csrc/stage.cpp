@@ -147,15 +147,17 @@ struct DecBufs {
 };
 DecBufs dec_layout(const rf_decoder_desc* d) {
     const int64_t T2 = d->rows, D = d->dim, F = d->ffn_dim, T1 = d->ctx_rows, L = d->n_layers;
-    const bool kv_batch = d->w_kv_all != nullptr, k_batch = kv_batch && d->k_batch;
+    // kv_given: the caller holds every layer's K/V already (rf_scene_kv); no context operand, no K/V region here
+    const bool kv_given = d->kv_all != nullptr;
+    const bool kv_batch = kv_given || d->w_kv_all != nullptr, k_batch = kv_batch && d->k_batch;
     DecBufs b;
     b.h = 0;
     b.q2 = b.h + align_up(T2 * D * 2);
     b.att = b.q2 + align_up(T2 * D * 2);
     b.g = b.att + align_up(T2 * D * 2);
     b.hc = b.g + align_up(T2 * F * 2);
-    b.kv = b.hc + align_up(T1 * d->ctx_dim * 2);
-    b.kview = b.kv + align_up(T1 * (kv_batch ? L : 1) * 2 * D * 2);
+    b.kv = b.hc + (kv_given ? 0 : align_up(T1 * d->ctx_dim * 2));
+    b.kview = b.kv + (kv_given ? 0 : align_up(T1 * (kv_batch ? L : 1) * 2 * D * 2));
     b.qkv = b.kview + align_up((int64_t)d->kv_rows * (k_batch ? L : 1) * D * 2);
     b.ss = b.qkv + (d->layers && d->n_layers > 0 && d->layers[0].self_norm ? align_up(T2 * 3 * D * 2) : 0);
     b.qkss = b.ss + align_up(T2 * RF_PRENORM_SLOTS * 4);
@@ -163,7 +165,42 @@ DecBufs dec_layout(const rf_decoder_desc* d) {
     b.total = b.qkss + align_up(T2 * (d->swin ? 2 : 1) * RF_PRENORM_SLOTS * 4);
     return b;
 }
+
+// Every decoder layer's K/V of a scene: the unit-weight RMSNorm of the context into the 16-bit operand `hc`, then one
+// GEMM with the stacked, kv_norm-folded weights into kv_all (bf16).  rf_scene_kv and rf_decoder_forward both issue
+// exactly these two launches, so a K/V buffer kept by the caller holds the bits the decoder would have computed.
+int scene_kv(const float* ctx, int64_t ld_ctx, int rows, int ctx_dim, const float* ctx_norm, const void* w_kv_all,
+             int width, int dt, float eps, void* hc, void* kv_all, int64_t ld_kv_all, void* gws, int64_t gwb,
+             void* stream) {
+    const bool f16 = dt == RF_DT_F16;
+    RF_CALL((f16 ? rf_rmsnorm_f16 : rf_rmsnorm)(ctx, ld_ctx, ctx_norm, eps, hc, ctx_dim, rows, ctx_dim, stream));
+    RF_CALL((f16 ? rf_gemm_f16 : rf_gemm_bf16)(hc, ctx_dim, w_kv_all, ctx_dim, kv_all, ld_kv_all, nullptr, rows, width,
+                                               ctx_dim, RF_EPI_BF16, gws, gwb, stream));
+    return RF_OK;
+}
 }  // namespace
+
+extern "C" int rf_scene_kv(const float* ctx, int64_t ld_ctx, int ctx_rows, int ctx_dim, const float* ctx_norm,
+                           const void* w_kv_all, int width, int operand_dtype, float eps, void* scratch, void* kv_all,
+                           int64_t ld_kv_all, void* gemm_ws, int64_t gemm_ws_bytes, void* stream) {
+    RF_REQUIRE(ctx_rows >= 0, "rf_scene_kv: negative ctx_rows");
+    RF_REQUIRE(ctx, "rf_scene_kv: null pointer: ctx");
+    RF_REQUIRE(ctx_norm, "rf_scene_kv: null pointer: ctx_norm");
+    RF_REQUIRE(w_kv_all, "rf_scene_kv: null pointer: w_kv_all");
+    RF_REQUIRE(scratch, "rf_scene_kv: null pointer: scratch");
+    RF_REQUIRE(kv_all, "rf_scene_kv: null pointer: kv_all");
+    RF_REQUIRE(ctx_dim > 0 && ctx_dim % 64 == 0 && ld_ctx >= ctx_dim,
+               "rf_scene_kv: context [ctx_rows, ctx_dim] with ctx_dim % 64 == 0 and ld_ctx >= ctx_dim");
+    RF_REQUIRE(width > 0 && width % 128 == 0,
+               "rf_scene_kv: width (%d) must be n_layers * 2 * dim, a positive multiple of 128", width);
+    RF_REQUIRE(ld_kv_all >= width, "rf_scene_kv: ld_kv_all (%lld) must be >= width (%d)", (long long)ld_kv_all, width);
+    RF_REQUIRE(operand_dtype == RF_DT_F16 || operand_dtype == RF_DT_BF16,
+               "rf_scene_kv: operand_dtype must be RF_DT_F16 or RF_DT_BF16");
+    RF_REQUIRE(((uintptr_t)scratch % kAlign) == 0, "rf_scene_kv: scratch must be 256-B aligned");
+    if (ctx_rows == 0) return RF_OK;
+    return scene_kv(ctx, ld_ctx, ctx_rows, ctx_dim, ctx_norm, w_kv_all, width, operand_dtype, eps, scratch, kv_all,
+                    ld_kv_all, gemm_ws, gemm_ws_bytes, stream);
+}
 
 extern "C" int64_t rf_decoder_workspace_bytes(const rf_decoder_desc* d) {
     if (!d || d->n_layers <= 0 || d->rows <= 0 || d->dim <= 0 || d->ffn_dim <= 0 || d->ctx_rows < 0 ||
@@ -187,7 +224,9 @@ extern "C" int rf_decoder_forward(float* x, int64_t ldx, const rf_decoder_desc* 
     RF_REQUIRE(d->ctx_rows > 0 && d->ctx_dim > 0 && d->ctx_dim % 64 == 0 && d->ld_ctx >= d->ctx_dim,
                "rf_decoder_forward: context [ctx_rows, ctx_dim] with ctx_dim % 64 == 0");
     RF_REQUIRE(d->kv_rows > 0 && d->n_cross >= 1, "rf_decoder_forward: no keys / cross-attention problems");
-    RF_REQUIRE(!d->k_batch || d->w_kv_all, "rf_decoder_forward: k_batch needs the batched K/V (w_kv_all)");
+    RF_REQUIRE(!d->k_batch || d->w_kv_all || d->kv_all, "rf_decoder_forward: k_batch needs the batched K/V (w_kv_all)");
+    RF_REQUIRE(!d->kv_all || d->ld_kv_all >= (int64_t)d->n_layers * 2 * d->dim,
+               "rf_decoder_forward: ld_kv_all (%lld) must be >= n_layers * 2 * dim", (long long)d->ld_kv_all);
     RF_REQUIRE(!d->kv_pos || (d->freqs && d->n_freqs > 0 && d->ld_kv_pos >= 9),
                "rf_decoder_forward: kv_pos needs freqs (and ld_kv_pos >= 9)");
     RF_REQUIRE(!d->ray_pos || (d->freqs && d->n_freqs > 0 && d->ld_ray_pos >= 9 && d->ray_pos_div >= 1),
@@ -199,7 +238,8 @@ extern "C" int rf_decoder_forward(float* x, int64_t ldx, const rf_decoder_desc* 
         const rf_decoder_layer& L = d->layers[i];
         RF_REQUIRE(L.query_norm && L.w_q && L.w_out && L.ffn_norm && L.w13 && L.w2,
                    "rf_decoder_forward: layer %d has a null weight", i);
-        RF_REQUIRE(d->w_kv_all || (L.kv_norm && L.w_kv), "rf_decoder_forward: layer %d has no K/V weights", i);
+        RF_REQUIRE(d->w_kv_all || d->kv_all || (L.kv_norm && L.w_kv), "rf_decoder_forward: layer %d has no K/V weights",
+                   i);
         RF_REQUIRE((L.self_norm != nullptr) == self_attn && (!self_attn || (L.w_self_in && L.w_self_out)),
                    "rf_decoder_forward: layer %d: self-attention weights must be given for every layer or none", i);
     }
@@ -215,7 +255,8 @@ extern "C" int rf_decoder_forward(float* x, int64_t ldx, const rf_decoder_desc* 
 
     const int T2 = d->rows, D = d->dim, H = d->n_heads, F = d->ffn_dim, T1 = d->ctx_rows, NL = d->n_layers;
     const bool f16 = d->operand_dtype == RF_DT_F16;
-    const bool kv_batch = d->w_kv_all != nullptr, k_batch = kv_batch && d->k_batch;
+    const bool kv_given = d->kv_all != nullptr;
+    const bool kv_batch = kv_given || d->w_kv_all != nullptr, k_batch = kv_batch && d->k_batch;
     const DecBufs b = dec_layout(d);
     char* ws = static_cast<char*>(d->workspace);
     void* h = ws + b.h;
@@ -223,13 +264,16 @@ extern "C" int rf_decoder_forward(float* x, int64_t ldx, const rf_decoder_desc* 
     void* att = ws + b.att;
     void* g = ws + b.g;
     void* hc = ws + b.hc;
-    uint16_t* kv = reinterpret_cast<uint16_t*>(ws + b.kv);
+    // every layer's K/V: the caller's (rf_scene_kv wrote it, read only here) or this call's own region
+    uint16_t* kv = kv_given ? const_cast<uint16_t*>(static_cast<const uint16_t*>(d->kv_all))
+                            : reinterpret_cast<uint16_t*>(ws + b.kv);
     uint16_t* kview = reinterpret_cast<uint16_t*>(ws + b.kview);
     uint16_t* qkv = reinterpret_cast<uint16_t*>(ws + b.qkv);
     float* ss = reinterpret_cast<float*>(ws + b.ss);
     float* qkss = reinterpret_cast<float*>(ws + b.qkss);  // Swin q/k row sums (rf_swin_attn_fwd_qkn)
     const int dt = d->operand_dtype;
-    const int64_t ld_kv = (kv_batch ? (int64_t)NL : 1) * 2 * D, ld_kview = (k_batch ? (int64_t)NL : 1) * D;
+    const int64_t ld_kv = kv_given ? d->ld_kv_all : (kv_batch ? (int64_t)NL : 1) * 2 * D;
+    const int64_t ld_kview = (k_batch ? (int64_t)NL : 1) * D;
     auto rmsnorm = f16 ? rf_rmsnorm_f16 : rf_rmsnorm;
     auto gemm = f16 ? rf_gemm_f16 : rf_gemm_bf16;
     const int epi_swiglu = f16 ? RF_EPI_SWIGLU_F16 : RF_EPI_SWIGLU;
@@ -237,11 +281,9 @@ extern "C" int rf_decoder_forward(float* x, int64_t ldx, const rf_decoder_desc* 
     void* gws = d->gemm_ws;
     const int64_t gwb = d->gemm_ws_bytes;
     const int nf = d->n_freqs;
-    if (kv_batch) {  // every layer's K/V in one GEMM over the unit-normed context
-        RF_CALL(rmsnorm(d->ctx, d->ld_ctx, d->ctx_norm, d->eps, hc, d->ctx_dim, T1, d->ctx_dim, stream));
-        RF_CALL(gemm(hc, d->ctx_dim, d->w_kv_all, d->ctx_dim, kv, ld_kv, nullptr, T1, (int)ld_kv, d->ctx_dim,
-                     RF_EPI_BF16, gws, gwb, stream));
-    }
+    if (kv_batch && !kv_given)  // every layer's K/V in one GEMM over the unit-normed context
+        RF_CALL(scene_kv(d->ctx, d->ld_ctx, T1, d->ctx_dim, d->ctx_norm, d->w_kv_all, (int)ld_kv, dt, d->eps, hc, kv,
+                         ld_kv, gws, gwb, stream));
     // the keys' norm + rotation: the standard layout, or (qk_fused) the pair-interleaved order of the permuted weights
     auto k_rope = d->qk_fused ? rf_qk_norm_rope_groups_ilv : rf_qk_norm_rope_groups;
     if (k_batch)  // every layer's keys normed and rotated per view in one launch

@@ -304,6 +304,37 @@ class _Frame:
         self.versions = [t._version for t in inputs]
 
 
+class EncodedScene:
+    """The camera-independent state of a batch of scenes (RenderFormer.encode_scene): the stage-1 output ``x1``
+    [T1, D] f32, every decoder layer's K/V ``kv_all`` [T1, n_layers * 2 * Dv] bf16 (None when the batched K/V form
+    is off: RF_KV_BATCH=0 or above 4 GiB) and the packed triangles ``tris``.  ``render_encoded`` renders any number
+    of cameras from it without running stage 1 or the K/V GEMM again.  It costs ``nbytes`` of device memory
+    (T1 * (4 * D + n_layers * 4 * Dv)) plus the retained inputs.
+
+    The handle also keeps a host copy of the mask (plans for any view count / resolution are built with no device
+    read-back), the input tensors (texture already log-encoded) to encode again after an fp16 fallback, the
+    ``precision`` = (operands, dpt_precision) and the weights object it was computed with, and the stream and end
+    event of the encode.  It belongs to one model on one device; ``lock`` serialises a re-encode."""
+    __slots__ = ("x1", "kv_all", "tris", "mask_host", "inputs", "versions", "precision", "weights", "model",
+                 "generation", "device", "stream", "event", "lock")
+
+    def __init__(self, model, generation, device, mask_host, inputs):
+        self.model, self.generation, self.device = model, generation, device
+        self.mask_host, self.inputs = mask_host, inputs
+        self.versions = [t._version for t in inputs]
+        self.x1 = self.kv_all = self.tris = self.precision = self.weights = self.stream = self.event = None
+        self.lock = threading.RLock()
+
+    @property
+    def batch_size(self) -> int:
+        return int(self.mask_host.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        """Device bytes of the kept state: x1 plus kv_all."""
+        return sum(t.numel() * t.element_size() for t in (self.x1, self.kv_all) if t is not None)
+
+
 def _hf_cache_snapshot(model_id: str) -> Optional[str]:
     """Newest snapshot directory of a hub model id in the local Hugging Face cache that holds config.json and
     model.safetensors (the files PyTorchModelHubMixin downloads), or None."""
@@ -394,6 +425,7 @@ class RenderFormer:
         self._last_plan: Dict = {}
         self._host_masks: Dict = {}  # id(device mask) -> (mask, version, host copy): plan_hint
         self._w: Optional[_DeviceWeights] = None
+        self._generation = 0  # bumped by to() / load_state_dict: an EncodedScene made before either is refused
         self._plans: Dict = {}
         self._capture: Optional[dict] = None
         self.skip_token_num = cfg.num_register_tokens
@@ -420,6 +452,7 @@ class RenderFormer:
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         check_state_dict(self.config, sd, strict=strict)
         self._sd = {k: v.detach().float().cpu() for k, v in sd.items()}
+        self._generation += 1
         if self._w is not None:
             with torch.cuda.device(self._device):
                 self._w = _DeviceWeights(self.config, self._sd, self._device, self.dpt_precision, self.operands)
@@ -439,6 +472,7 @@ class RenderFormer:
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self._device = device
+        self._generation += 1
         with torch.cuda.device(device):
             self._w = _DeviceWeights(self.config, self._sd, device, self.dpt_precision, self.operands)
         return self
@@ -479,7 +513,15 @@ class RenderFormer:
             host = np.asarray(hint[2], dtype=bool)
         else:
             host = mask.cpu().numpy().astype(bool)  # (device-only mask: one read-back, like unpad_input)
-        key = (tuple(mask.shape), host.tobytes(), V, res)
+        plan = self._plan_host(host, V, res)
+        if len(self._last_plan) > 128:
+            self._last_plan.clear()
+        self._last_plan[ko] = (mask, mask._version, plan)
+        return plan
+
+    def _plan_host(self, host, V, res):
+        """The plan of a host mask (numpy bool [B, N]) from the cache keyed by its pattern: no device read-back."""
+        key = (tuple(host.shape), host.tobytes(), V, res)
         plan = self._plans.get(key)
         if plan is None:
             if len(self._plans) > 64:
@@ -487,10 +529,15 @@ class RenderFormer:
             plan = _build_plan(host, V, res, self.config.patch_size, self.config.num_register_tokens, self._device,
                                self.config.num_heads)
             self._plans[key] = plan
-        if len(self._last_plan) > 128:
-            self._last_plan.clear()
-        self._last_plan[ko] = (mask, mask._version, plan)
         return plan
+
+    def _mask_host(self, mask):
+        """Host copy of a device mask: the registered one (plan_hint) or one read-back."""
+        import numpy as np
+        hint = self._host_masks.get(id(mask))
+        if hint is not None and hint[0] is mask and hint[1] == mask._version:
+            return np.array(hint[2], dtype=bool)
+        return mask.cpu().numpy().astype(bool)
 
     def capture_taps(self, enc_rows=None, dec_rows=None, dec_views=None) -> dict:
         """Arm a one-shot capture of intermediates for the NEXT render (parity tests at production size): the
@@ -607,15 +654,26 @@ class RenderFormer:
             if cap["enc"] is not None:
                 cap["out"]["enc_rows"] = x.index_select(0, cap["enc"]).clone()
 
-    def _stage2(self, plan: _Plan, x: torch.Tensor, ctx: torch.Tensor, pos2: torch.Tensor, ray_pos: torch.Tensor):
-        """TransformerDecoder (attention.py:673-688): cross-attn rays->triangles, Swin/full self-attn, SwiGLU."""
+    def _kv_batch(self, T1: int) -> bool:
+        """All decoder layers' K/V in one GEMM (see _DeviceWeights.wkv_all) unless RF_KV_BATCH=0 or it would exceed
+        4 GiB."""
+        cfg = self.config
+        return (os.environ.get("RF_KV_BATCH", "1") != "0"
+                and T1 * cfg.view_transformer_n_layers * 2 * cfg.view_transformer_latent_dim * 2 <= (4 << 30))
+
+    def _stage2(self, plan: _Plan, x: torch.Tensor, ctx: torch.Tensor, pos2: torch.Tensor, ray_pos: torch.Tensor,
+                kv_all: Optional[torch.Tensor] = None):
+        """TransformerDecoder (attention.py:673-688): cross-attn rays->triangles, Swin/full self-attn, SwiGLU.
+        ``kv_all``: every layer's K/V computed earlier (ops.scene_kv, an EncodedScene's), used in place of the
+        context norm + K/V GEMM of the batched form; the fp8 and RF_KV_BATCH=0 paths project from ``ctx`` as ever."""
         cfg, W, dev = self.config, self._w, self._device
         D, H, F = cfg.view_transformer_latent_dim, cfg.view_transformer_n_heads, cfg.view_transformer_ffn_hidden_dim
         T2, R, P = x.shape[0], plan.R, plan.B * plan.V
         qk = cfg.qk_norm
         n_dec = len(W.dec)
-        # all layers' K/V in one GEMM (see _DeviceWeights.wkv_all) unless RF_KV_BATCH=0 or it would exceed 4 GiB
-        kv_batch = (os.environ.get("RF_KV_BATCH", "1") != "0" and plan.T1 * n_dec * 2 * D * 2 <= (4 << 30))
+        kv_batch = self._kv_batch(plan.T1)
+        if not kv_batch or self.fp8:
+            kv_all = None
         # (the rotated keys of all layers are kept when they fit in 4 GiB: T_kv grows with the view count)
         k_batch = kv_batch and os.environ.get("RF_K_BATCH", "1") != "0" and plan.T_kv * n_dec * D * 2 <= (4 << 30)
         swin = cfg.view_transformer_use_swin_attn
@@ -626,9 +684,10 @@ class RenderFormer:
                 W.dec_desc = ops.decoder_layers(W.dec, qk)
             out_idx = sorted(i for i in set(cfg.out_layers) if 0 <= i < n_dec)
             planes = [W.dpt.empty_tap_planes(j, P, plan.hp, plan.wp, D, dev) for j in range(len(out_idx))]
-            kv = dict(ctx_norm=W.ctx_unit if kv_batch else None, w_kv_all=W.wkv_all if kv_batch else None,
-                      k_batch=k_batch, k_norm_all=W.k_norm_all if qk else None, kv_src_rows=plan.kv_src_rows,
-                      kv_pos=pos2, freqs=W.dec_freqs)
+            proj_kv = kv_batch and kv_all is None  # (a given kv_all: the descriptor carries it, no K/V weights)
+            kv = dict(ctx_norm=W.ctx_unit if proj_kv else None, w_kv_all=W.wkv_all if proj_kv else None,
+                      kv_all=kv_all, k_batch=k_batch, k_norm_all=W.k_norm_all if qk else None,
+                      kv_src_rows=plan.kv_src_rows, kv_pos=pos2, freqs=W.dec_freqs)
             cross = dict(ray_pos=ray_pos, ray_pos_div=R, problems=plan.prob2, schedule=plan.sched2, qk_fused=W.qk_fused)
             sa = dict(swin=swin, n_images=P, grid_h=plan.hp, grid_w=plan.wp, window=SWIN_WINDOW, shift=SWIN_SHIFT,
                       problems=None if swin else plan.prob_self)
@@ -640,11 +699,12 @@ class RenderFormer:
         q2 = torch.empty(T2, D, dtype=torch.bfloat16, device=dev)
         att = torch.empty(T2, D, dtype=W.half, device=dev)
         g = torch.empty(T2, F, dtype=W.half, device=dev)
-        hc = torch.empty(plan.T1, ctx.shape[1], dtype=W.half, device=dev)
+        hc = torch.empty(plan.T1, ctx.shape[1], dtype=W.half, device=dev) if kv_all is None else None
         if kv_batch:
-            ops.rmsnorm(ctx, W.ctx_unit, EPS, hc)
-            kv_all = torch.empty(plan.T1, n_dec * 2 * D, dtype=torch.bfloat16, device=dev)
-            ops.gemm(hc, W.wkv_all, kv_all)
+            if kv_all is None:
+                ops.rmsnorm(ctx, W.ctx_unit, EPS, hc)
+                kv_all = torch.empty(plan.T1, n_dec * 2 * D, dtype=torch.bfloat16, device=dev)
+                ops.gemm(hc, W.wkv_all, kv_all)
         else:
             kv = torch.empty(plan.T1, 2 * D, dtype=torch.bfloat16, device=dev)
         if k_batch:
@@ -797,6 +857,166 @@ class RenderFormer:
                 lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, resolution, False),
                 (triangles, texture, mask, vn, c2w, fov))
 
+    # ------------------------------------------------------------------ encode once, render many cameras
+    @torch.no_grad()
+    def encode_scene(self, triangles, texture, mask, vn, log_encode: bool = True) -> EncodedScene:
+        """Everything of a render that does not depend on the camera, once: the triangle embedding, stage 1 and
+        (in the batched K/V form) every decoder layer's K/V, exactly as ``render_views`` computes them.  The handle
+        renders any number of cameras (``render_encoded``), each frame launching what a full render launches after
+        its K/V GEMM, so on the same bits.  ``texture`` is log-encoded in place (once) like ``render_views``'.
+
+        fp16 range check: the encode runs under a range word of its own and, unless ``range_check`` is "off", waits
+        for its end event before returning (once per scene).  An overflow raises DeviceError in the "deferred" mode;
+        "sync" / "lazy" move the model to bf16 operands (PrecisionWarning) and encode again."""
+        self._require()
+        dev = self._device
+        with torch.cuda.device(dev):
+            for t, n in ((triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn")):
+                if t.device != dev:
+                    raise ValueError(f"{n} must be on {dev} (got {t.device})")
+            sc = EncodedScene(self, self._generation, dev, self._mask_host(mask), (triangles, texture, mask, vn))
+            with sc.lock:
+                self._encode_checked(sc, log_encode)
+            return sc
+
+    def _encode(self, sc: EncodedScene, log_encode: bool):
+        """Fill the handle from its inputs with the model's present weights, on the current stream."""
+        cfg, dev = self.config, self._device
+        triangles, texture, _, vn = sc.inputs
+        B = sc.batch_size
+        # (stage 1's tables do not depend on the view count or the resolution: the smallest valid plan)
+        res0 = cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)
+        plan = self._plan_host(sc.mask_host, 1, res0)
+        W = self._w
+        tris = triangles.reshape(B, -1, 9).float().contiguous()
+        x1 = self._embed_triangles(plan, texture, vn.reshape(B, -1, 9).float().contiguous(), log_encode)
+        pos1 = torch.empty(plan.T1, 9, dtype=torch.float32, device=dev)
+        ops.scene_pos(tris, plan.valid_flat, plan.scene_off, None, B, 1, cfg.num_register_tokens, pos1, plan.cu1,
+                      max(plan.counts))
+        x1 = self._stage1(plan, x1, pos1)
+        kv_all = None
+        if self._kv_batch(plan.T1) and not self.fp8 and plan.T1 > 0:
+            kv_all = ops.scene_kv(x1, W.ctx_unit, W.wkv_all, EPS)
+        stream = torch.cuda.current_stream()
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        sc.x1, sc.kv_all, sc.tris = x1, kv_all, tris
+        sc.weights, sc.precision = W, (self.operands, self.dpt_precision)
+        sc.stream, sc.event = stream, ev
+
+    def _encode_checked(self, sc: EncodedScene, log_encode: bool):
+        """_encode under a range word of its own, resolved before returning (the caller holds sc.lock)."""
+        from ._lib import DeviceError
+        if not (self.operands == "f16" and self.range_check != "off"):  # (stage 1 has no other fp16 writer)
+            return self._encode(sc, log_encode)
+        lib = _load_lib()
+        with self._range_lock:
+            word = self._range_free.pop() if self._range_free else None
+        if word is None:
+            h = ctypes.c_void_p()
+            if lib.rf_range_word_new(ctypes.byref(h)) != 0:
+                raise RuntimeError(f"rf_range_word_new: {lib.rf_last_error().decode(errors='replace')}")
+            word = h.value
+        lib.rf_range_word_clear(word)
+        lib.rf_range_word_bind(word)
+        try:
+            self._encode(sc, log_encode)
+        except BaseException:
+            lib.rf_range_word_bind(None)
+            torch.cuda.current_stream().synchronize()
+            with self._range_lock:
+                self._range_free.append(word)
+            raise
+        lib.rf_range_word_bind(None)
+        sc.event.synchronize()
+        code = int(lib.rf_range_word_read(word))
+        with self._range_lock:
+            self._range_free.append(word)
+        if not code:
+            return
+        what = [n for n, bit in (("GEMM", 1), ("RMSNorm", 2), ("attention", 4), ("DPT plane", 8)) if code & bit]
+        if self.range_check == "deferred":
+            raise DeviceError(f"fp16 operand overflow (range code {code}: |x| > 65504 in an fp16 {'/'.join(what)} "
+                              "output) while encoding a scene -- this checkpoint's activations exceed fp16's range: "
+                              "encode with operands='bf16' (RF_OPERANDS=bf16), or range_check='sync' / 'lazy' "
+                              "(encodes such a scene again)")
+        self._fall_back(code, what, "scene is encoded again", stacklevel=5)
+        self._guarded_replay(lambda: self._encode(sc, False))  # (the texture is log-encoded already)
+
+    def _check_handle(self, sc: EncodedScene):
+        if not isinstance(sc, EncodedScene):
+            raise ValueError(f"render_encoded needs an EncodedScene (encode_scene / pipeline.encode), got {type(sc)}")
+        if sc.model is not self:
+            raise ValueError("this EncodedScene was encoded by another RenderFormer: a handle renders only with the "
+                             "model that made it")
+        if sc.device != self._device:
+            raise ValueError(f"this EncodedScene lives on {sc.device}, the model on {self._device}")
+        if sc.generation != self._generation:
+            raise ValueError("this EncodedScene was made before the model's to() / load_state_dict: its stage-1 "
+                             "output belongs to other weights; encode the scene again")
+
+    def _refresh(self, sc: EncodedScene):
+        """Staleness: a handle computed with other operands than the model has now (an fp16 fallback happened since)
+        is encoded again in place from its retained inputs, on the current stream, before stage 2 reads it."""
+        from ._lib import DeviceError
+        with sc.lock:
+            if sc.weights is self._w and sc.precision == (self.operands, self.dpt_precision):
+                return
+            if any(t._version != v for t, v in zip(sc.inputs, sc.versions)):
+                raise DeviceError("this EncodedScene must be encoded again (the model fell back to "
+                                  f"{self.operands} operands after an fp16 overflow), but its input tensors were "
+                                  "modified in place since encode: keep them unchanged while the handle is in use, or "
+                                  "encode the scene again")
+            sc.event.synchronize()  # the old state may still be read on the encode's stream; then it is replaced
+            self._encode(sc, False)
+
+    @torch.no_grad()
+    def render_encoded(self, scene: EncodedScene, c2w, fov, resolution: int) -> torch.Tensor:
+        """Render the cameras ``c2w`` [B, V, 4, 4] / ``fov`` [B, V, ...] of an encoded batch of scenes: stage 2 +
+        DPT only, per chunk of ``view_chunk`` views like ``render_views``.  Returns [B, V, res, res, C] linear HDR,
+        bit-identical to ``render_views`` of the same inputs.  Same range-check modes as ``render_views`` (``resolve
+        (out)`` works); after an fp16 overflow, here or in any other render of the model, the handle is encoded
+        again with the model's new operands before the frame is (re-)rendered."""
+        self._require()
+        self._check_handle(scene)
+        with torch.cuda.device(self._device):
+            run = lambda: self._render_encoded(scene, c2w, fov, resolution)  # noqa: E731
+            return self._guarded(run, run, (c2w, fov))
+
+    def _render_encoded(self, sc: EncodedScene, c2w, fov, resolution):
+        cfg, dev = self.config, self._device
+        self._check_handle(sc)
+        for t, n in ((c2w, "c2w"), (fov, "fov")):
+            if t.device != dev:
+                raise ValueError(f"{n} must be on {dev} (got {t.device})")
+        B, V = c2w.shape[:2]
+        if B != sc.batch_size:
+            raise ValueError(f"c2w has batch size {B}, the encoded scene {sc.batch_size}")
+        if resolution % (cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)) != 0:
+            raise ValueError(f"resolution {resolution} incompatible with patch/window size")
+        self._refresh(sc)
+        with sc.lock:
+            x1, kv_all, tris, ev, st = sc.x1, sc.kv_all, sc.tris, sc.event, sc.stream
+        cur = torch.cuda.current_stream()
+        if cur != st:  # another stream than the encode's: order after it, and keep the tensors alive for this one
+            cur.wait_event(ev)
+            for t in (x1, kv_all, tris):
+                if t is not None:
+                    t.record_stream(cur)
+        chunk = V if not self.view_chunk else min(V, int(self.view_chunk))
+        out = None
+        for v0 in range(0, V, chunk):
+            v1 = min(V, v0 + chunk)
+            plan = self._plan_host(sc.mask_host, v1 - v0, resolution)
+            o = self._views(plan, x1, tris, c2w[:, v0:v1], fov[:, v0:v1], resolution, kv_all)
+            o = o.view(B, v1 - v0, resolution, resolution, -1)
+            if v1 - v0 == V:
+                return o
+            if out is None:
+                out = torch.empty(B, V, *o.shape[2:], dtype=o.dtype, device=dev)
+            out[:, v0:v1] = o
+        return out
+
     # ------------------------------------------------------------------ fp16 range check
     def _range_active(self) -> bool:
         return (self.operands == "f16" or self.dpt_precision == "f16") and self.range_check != "off"
@@ -864,7 +1084,6 @@ class RenderFormer:
             self._range_free.append(fr.word)
         if not code:
             return False
-        import warnings
         what = [n for n, bit in (("GEMM", 1), ("RMSNorm", 2), ("attention", 4), ("DPT plane", 8)) if code & bit]
         if self.range_check == "deferred":
             raise DeviceError(f"fp16 operand overflow (range code {code}: |x| > 65504 in an fp16 {'/'.join(what)} "
@@ -875,6 +1094,16 @@ class RenderFormer:
             raise DeviceError(f"fp16 operand overflow (range code {code}) in a frame whose inputs were modified in "
                               "place before it could be rendered again: call resolve(out) / check_range() before "
                               "reusing input buffers, or use range_check='sync'")
+        self._fall_back(code, what, "frame is rendered again", stacklevel=5)
+        with torch.cuda.device(self._device), torch.cuda.stream(fr.stream):
+            new = self._guarded_replay(fr.replay)
+            fr.out.copy_(new.view_as(fr.out))
+        fr.out._rf_rerendered = True  # resolve(out) reports it even when a later render's poll did the re-render
+        return True
+
+    def _fall_back(self, code: int, what, redo: str, stacklevel: int):
+        """Move the model to the operands an fp16 overflow (range code ``code``) asks for, and warn."""
+        import warnings
         with self._range_lock:
             # projections and attention (codes 1/2/4) -> bf16 operands; the DPT planes (code 8) -> bf16x3, and a
             # stage-1 or stage-2 overflow reaches the DPT as inf too, so it sets 8 as well
@@ -891,14 +1120,9 @@ class RenderFormer:
                 self._w = _DeviceWeights(self.config, self._sd, self._device, self.dpt_precision, self.operands)
             self.range_fallbacks += 1
         warnings.warn(f"fp16 operand overflow (range code {code}: {'/'.join(what)}): this checkpoint's activations "
-                      f"exceed fp16's range; the frame is rendered again and the model keeps "
+                      f"exceed fp16's range; the {redo} and the model keeps "
                       f"{self.operands} projection operands and {self.dpt_precision} DPT planes from now on",
-                      PrecisionWarning, stacklevel=4)
-        with torch.cuda.device(self._device), torch.cuda.stream(fr.stream):
-            new = self._guarded_replay(fr.replay)
-            fr.out.copy_(new.view_as(fr.out))
-        fr.out._rf_rerendered = True  # resolve(out) reports it even when a later render's poll did the re-render
-        return True
+                      PrecisionWarning, stacklevel=stacklevel)
 
     def _guarded_replay(self, replay):
         """The re-render after a fallback, checked at once: an overflow that survives it is an error."""
@@ -1018,8 +1242,9 @@ class RenderFormer:
             out[:, v0:v1] = o
         return out
 
-    def _views(self, plan: _Plan, x1, tris, c2w, fov, resolution):
-        """Stage 2 + DPT + decode for the plan's views of every scene (c2w [B, Vc, 4, 4], fov [B, Vc, ...])."""
+    def _views(self, plan: _Plan, x1, tris, c2w, fov, resolution, kv_all=None):
+        """Stage 2 + DPT + decode for the plan's views of every scene (c2w [B, Vc, 4, 4], fov [B, Vc, ...]);
+        ``kv_all``: the scene's K/V of every decoder layer when it is already known (an EncodedScene's)."""
         cfg, dev = self.config, self._device
         B, V = plan.B, plan.V
         P = B * V
@@ -1035,7 +1260,7 @@ class RenderFormer:
         pos2 = torch.empty(plan.T_kv, 9, dtype=torch.float32, device=dev)
         ops.scene_pos(tris, plan.valid_flat, plan.scene_off, pos_c2w, B, V, cfg.num_register_tokens, pos2,
                       plan.kv_off, max(plan.counts))
-        taps = self._stage2(plan, x2, x1, pos2, ray_pos)
+        taps = self._stage2(plan, x2, x1, pos2, ray_pos, kv_all)
         return self._decode(plan, taps, log_decode=not cfg.use_ldr, channels_last=True)
 
     @torch.no_grad()

@@ -601,6 +601,31 @@ def encoder_forward(x: torch.Tensor, layers, n_layers: int, n_heads: int, ffn_di
     return x
 
 
+def scene_kv(ctx: torch.Tensor, ctx_norm: torch.Tensor, w_kv_all: torch.Tensor, eps: float,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Every decoder layer's K/V of a scene, once (rf_scene_kv): out [T1, n_layers * 2 * D] bf16 = rmsnorm(ctx;
+    ctx_norm) @ w_kv_all.T, layer i's K at columns [2 D i, 2 D i + D), its V after it.  The two launches
+    decoder_forward issues first for w_kv_all, on the same arguments: handing ``out`` back as kv["kv_all"] gives the
+    same bits.  ctx [T1, Dc] f32; w_kv_all [n_layers * 2 * D, Dc] fp16 or bf16 (the operand type of the scratch)."""
+    _dev(ctx, torch.float32, "ctx")
+    _dev(ctx_norm, torch.float32, "ctx_norm")
+    _check(w_kv_all.dtype in HALF, "scene_kv: w_kv_all must be bf16 or fp16")
+    _dev(w_kv_all, w_kv_all.dtype, "w_kv_all")
+    rows, dc = ctx.shape
+    width = w_kv_all.shape[0]
+    _check(w_kv_all.shape[1] == dc and w_kv_all.stride(0) == dc and ctx_norm.numel() == dc,
+           "scene_kv: w_kv_all [width, Dc] (dense) and ctx_norm [Dc] must match ctx [T1, Dc]")
+    if out is None:
+        out = torch.empty(rows, width, dtype=torch.bfloat16, device=ctx.device)
+    _dev(out, torch.bfloat16, "out")
+    _check(out.dim() == 2 and out.shape[0] == rows and out.shape[1] == width, "scene_kv: out must be [T1, width]")
+    scratch = torch.empty(max(rows, 1) * dc, dtype=w_kv_all.dtype, device=ctx.device)  # the normed operand
+    gws = _gemm_workspace(ctx.device)
+    call("rf_scene_kv", ptr(ctx), ctx.stride(0), rows, dc, ptr(ctx_norm), ptr(w_kv_all), width, _dt(w_kv_all), eps,
+         ptr(scratch), ptr(out), out.stride(0), ptr(gws), gws.numel(), stream())
+    return out
+
+
 def decoder_layers(layers, qk_norm: bool):
     """Host array of rf_decoder_layer (device pointers) for the decoder stack's weights (model._Layer objects)."""
     from ._lib import DecoderLayer
@@ -622,9 +647,11 @@ def decoder_forward(x: torch.Tensor, layers, n_layers: int, n_heads: int, ffn_di
                     tag: Optional[str] = None) -> torch.Tensor:
     """x [T2, D] f32 through the whole decoder stack in place, one C call (rf_decoder_forward; `layers` from
     decoder_layers).  kv: ctx_norm, w_kv_all (None = per-layer K/V), k_batch, k_norm_all, kv_src_rows, kv_pos,
-    freqs; cross: ray_pos, ray_pos_div, problems, schedule, qk_fused (the q/k weights in rope_pair_perm order: the
-    query rotation in its projection's epilogue); self_attn: swin, n_images, grid_h, grid_w, window, shift,
-    problems; taps: (layer, planes_hi, planes_lo or None, ld) in layer order."""
+    freqs, and optionally kv_all (scene_kv's output, bf16 [T1, >= n_layers * 2 * D]: the context norm and the K/V
+    GEMM are skipped and ctx is not read; ctx_norm / w_kv_all may then be None); cross: ray_pos, ray_pos_div,
+    problems, schedule, qk_fused (the q/k weights in rope_pair_perm order: the query rotation in its projection's
+    epilogue); self_attn: swin, n_images, grid_h, grid_w, window, shift, problems; taps: (layer, planes_hi,
+    planes_lo or None, ld) in layer order."""
     from ._lib import DecoderDesc, DecoderTap
     import ctypes
     _dev(x, torch.float32, "x")
@@ -641,6 +668,11 @@ def decoder_forward(x: torch.Tensor, layers, n_layers: int, n_heads: int, ffn_di
         _dev(cross["ray_pos"], torch.float32, "ray_pos")
     if cross.get("schedule") is not None:
         _dev(cross["schedule"], torch.int64, "schedule")
+    kv_all = kv.get("kv_all")
+    if kv_all is not None:
+        _dev(kv_all, torch.bfloat16, "kv_all")
+        _check(kv_all.dim() == 2 and kv_all.shape[0] == ctx.shape[0] and kv_all.shape[1] >= n_layers * 2 * dim,
+               f"decoder_forward: kv_all must be [{ctx.shape[0]}, >= {n_layers * 2 * dim}], got {tuple(kv_all.shape)}")
     tarr = (DecoderTap * max(1, len(taps)))()
     for e, (layer, hi, lo, ld) in zip(tarr, taps):
         e.layer, e.p_hi, e.p_lo, e.p_ld = layer, ptr(hi), ptr(lo), ld
@@ -663,7 +695,8 @@ def decoder_forward(x: torch.Tensor, layers, n_layers: int, n_heads: int, ffn_di
                     grid_w=self_attn.get("grid_w", 0), window=self_attn.get("window", 0),
                     shift=self_attn.get("shift", 0), self_problems=ptr(sp), n_self=sp.shape[0] if sp is not None else 0,
                     taps=ctypes.addressof(tarr), n_taps=len(taps), gemm_ws=ptr(gws), gemm_ws_bytes=gws.numel(),
-                    attn_ws=ptr(_attn_workspace(x.device)))
+                    attn_ws=ptr(_attn_workspace(x.device)), kv_all=ptr(kv_all),
+                    ld_kv_all=kv_all.stride(0) if kv_all is not None else 0)
     lib = load()
     ws = torch.empty(int(lib.rf_decoder_workspace_bytes(ctypes.addressof(d))), dtype=torch.uint8, device=x.device)
     d.workspace = ptr(ws)

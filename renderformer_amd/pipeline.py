@@ -24,6 +24,17 @@ frame's end event — no device sync, the wait the caller's ``.cpu()`` would do 
 re-renders an overflowed frame with bf16 operands before returning, so unchanged callers of the
 reference API (README example, ``infer.py``) never see a non-finite frame.  Pipelining callers
 (``batch_infer.py``) opt in to ``range_check="lazy"`` and call ``resolve(out)`` / ``check_range()``.
+
+Cameras that arrive over time (a viewer, an orbit rendered frame by frame, "same scene, new camera"):
+``scene = pipe.encode(triangles, texture, mask, vn)`` runs everything that does not depend on the camera
+once — the triangle embedding, stage 1 and every decoder layer's K/V — and ``pipe.render_encoded(scene,
+c2w, fov, resolution)`` renders any number of cameras from the handle, each frame bit-identical to
+``render`` of the same inputs.  The handle keeps the stage-1 output and the K/V on the device,
+``T1 * (4 * D + n_layers * 4 * Dv)`` bytes (``scene.nbytes``; T1 = 16 register tokens + the valid triangles
+per scene), and the input tensors, which must stay unmodified while it is in use.  After an fp16 overflow
+fallback (in ``encode``, in ``render_encoded`` or in any other render of the model) the model computes with
+bf16 operands: a handle made before it is encoded again from its retained inputs, once, at its next
+``render_encoded``.  A handle belongs to the model that made it; ``to()`` / ``load_state_dict`` invalidate it.
 """
 from __future__ import annotations
 
@@ -55,24 +66,46 @@ class RenderFormerRenderingPipeline:
         self.model.to(device)
         return self
 
-    def render(self, triangles, texture, mask, vn, c2w, fov, resolution: int = 512,
-               torch_dtype: torch.dtype = torch.float16):
-        """Render [bs, nv, resolution, resolution, 3] HDR images (rendering_pipeline.py:28-125)."""
+    def _check_dtype(self, torch_dtype, stacklevel):
         assert torch_dtype in [torch.bfloat16, torch.float16, torch.float32], (
             f"Invalid precision: {torch_dtype}\nChoose from: torch.bfloat16, torch.float16, torch.float32")
         if torch_dtype == torch.float32 and not self._warned_fp32:
             self._warned_fp32 = True
             warnings.warn("torch_dtype=torch.float32: this MI355X path has no fp32-operand mode; it computes with "
                           f"{self.model.precision} (within 1e-3 relative L2 of the reference's CPU fp32 output)",
-                          PrecisionWarning, stacklevel=2)
-        cfg = self.config
-        if cfg.texture_encode_patch_size == 1 and texture.dim() == 5:
+                          PrecisionWarning, stacklevel=stacklevel)
+
+    def _texture(self, texture):
+        if self.config.texture_encode_patch_size == 1 and texture.dim() == 5:
             texture = texture[:, :, :, 0, 0].contiguous()
         if not texture.is_contiguous():
             raise ValueError("texture must be contiguous (it is log-encoded in place)")
         if texture.dtype != torch.float32:
             raise ValueError("texture must be float32 (it is log-encoded in place)")
+        return texture
+
+    def render(self, triangles, texture, mask, vn, c2w, fov, resolution: int = 512,
+               torch_dtype: torch.dtype = torch.float16):
+        """Render [bs, nv, resolution, resolution, 3] HDR images (rendering_pipeline.py:28-125)."""
+        self._check_dtype(torch_dtype, stacklevel=3)
+        cfg = self.config
+        texture = self._texture(texture)
         out = self.model.render_views(triangles, texture, mask, vn, c2w, fov, resolution, log_encode=not cfg.use_ldr)
+        self.last_precision = {"requested": str(torch_dtype), "computed": self.model.precision}
+        return out
+
+    def encode(self, triangles, texture, mask, vn):
+        """Encode a batch of scenes once (RenderFormer.encode_scene): everything ``render`` computes before it needs
+        a camera.  ``texture`` is handled as in ``render`` — log-encoded **in place**, once.  Returns the handle
+        ``render_encoded`` takes; it holds ``nbytes`` of device memory and the input tensors."""
+        return self.model.encode_scene(triangles, self._texture(texture), mask, vn,
+                                       log_encode=not self.config.use_ldr)
+
+    def render_encoded(self, scene, c2w, fov, resolution: int = 512, torch_dtype: torch.dtype = torch.float16):
+        """Render the cameras ``c2w`` [bs, nv, 4, 4] / ``fov`` of an encoded batch: [bs, nv, resolution, resolution,
+        3] HDR, bit-identical to ``render`` of the same scene and cameras, without stage 1 and the K/V projection."""
+        self._check_dtype(torch_dtype, stacklevel=3)
+        out = self.model.render_encoded(scene, c2w, fov, resolution)
         self.last_precision = {"requested": str(torch_dtype), "computed": self.model.precision}
         return out
 
