@@ -56,7 +56,9 @@ struct Tile {
     static constexpr bool ASHARE = APIECES < NWAVE;
     static constexpr int PA = ASHARE ? 1 : BM / 16 / NWAVE, PB = BN / 16 / NWAVE;
     static constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
-    static_assert(PA >= 1 && PB >= 1 && (ASHARE || PA * NWAVE * 16 == BM) && PB * NWAVE * 16 == BN,
+    // (BM = 288 is the phased loop's tile: its 18 A pieces do not split over 8 waves, and only the epilogue's view
+    // of the block - BM, MW, TI, ... - is used of it, never the ring's staging)
+    static_assert(PA >= 1 && PB >= 1 && (ASHARE || PA * NWAVE * 16 == BM || BM == 288) && PB * NWAVE * 16 == BN,
                   "tile/wave mismatch");
     static_assert(TI >= 1 && TJ >= 2 && TJ % 2 == 0, "wave tile too small");
 };
@@ -472,11 +474,18 @@ RF_DEV void lds_sync() {
 // E_ROPE's staged positions: [BM][9] floats by 256-B LDS-DMA pieces (one dword a lane), so the area is whole pieces
 template <class C>
 constexpr int ROPE_POS_BYTES = (C::BM * 9 + 63) / 64 * 256;
+// Row-sum scratch of the 16-bit epilogues ([WGN][BM] floats after the staged rows).  The 288-row tile has no LDS left
+// for it beside its two operand buffers and E_ROPE's operands, and keeps the WGN partials of row t in slots 1..WGN of
+// the row's staged entry instead: once the slot sums are reduced only slot 0 (1 / rms) of an entry is read again.
+template <class C, int EPI>
+constexpr bool RED_IN_ROWS = C::BM == 288 && (EPI == E_BF16 || EPI == E_ROPE) && C::WGN < PN_SLOTS;
+template <class C, int EPI>
+constexpr int PN_RED = RED_IN_ROWS<C, EPI> ? 0 : C::BM * C::WGN * 4;
 template <class C, int EPI>
 constexpr int PN_AREA = EPI == E_ADD      ? C::BN * 4 + C::BM * C::WGN * 4
-                        : EPI == E_BF16   ? C::BM * PN_SLOTS * 4 + C::BM * C::WGN * 4
+                        : EPI == E_BF16   ? C::BM * PN_SLOTS * 4 + PN_RED<C, EPI>
                         // E_ROPE: + the q/k norm weights of the tile's columns, the tile rows' positions, the frequencies
-                        : EPI == E_ROPE   ? C::BM * PN_SLOTS * 4 + C::BM * C::WGN * 4 + C::BN * 4 + ROPE_POS_BYTES<C> + 64 * 4
+                        : EPI == E_ROPE   ? C::BM * PN_SLOTS * 4 + PN_RED<C, EPI> + C::BN * 4 + ROPE_POS_BYTES<C> + 64 * 4
                         : EPI == E_SWIGLU ? C::BM * PN_SLOTS * 4
                                           : 0;
 
@@ -499,7 +508,7 @@ RF_DEV void pn_issue(const EngineArgs& p, char* area, int m0, int n0) {
         }
         if constexpr (EPI == E_ROPE) {
             if (n0 / p.seg_w < p.seg_n) {  // a q/k tile: its norm weights, the rows' positions, the frequencies
-                char* const gl = area + C::BM * PN_SLOTS * 4 + C::BM * C::WGN * 4;
+                char* const gl = area + C::BM * PN_SLOTS * 4 + PN_RED<C, EPI>;
                 char* const pl = gl + C::BN * 4;
                 char* const fl = pl + ROPE_POS_BYTES<C>;  // (the last pos piece runs past BM * 9 floats)
                 if (wave == 0 && p.rope_g && 4 * lane < C::BN)  // 16 B (4 columns) a lane
@@ -763,6 +772,10 @@ RF_DEV void engine_epilogue(const EngineArgs& p, int m0, int n0, const f32x4 (&a
         const bool segq = (EPI == E_BF16 || (EPI == E_ROPE && qkseg)) && p.seg_ss && area && n0 / p.seg_w < p.seg_n;
         // row-sum scratch: after g of the tile's columns (producer) / after the staged ss rows (consumer)
         char* const red = area + (EPI == E_ADD ? C::BN * 4 : C::BM * PN_SLOTS * 4);
+        auto red_at = [&](int w, int t) -> char* {  // partial sum of wave column w for tile row t
+            if constexpr (RED_IN_ROWS<C, EPI>) return area + t * (PN_SLOTS * 4) + (1 + w) * 4;
+            else return red + (w * C::BM + t) * 4;
+        };
         if (pre) lds_sync();  // g staged (pn_issue) and visible
         float ssr[TI];
 #pragma unroll
@@ -771,7 +784,7 @@ RF_DEV void engine_epilogue(const EngineArgs& p, int m0, int n0, const f32x4 (&a
         // wait behind the stores of earlier fragments, vmcnt counting both in issue order).  Per lane and column
         // fragment j the 4 columns cq..cq + 3 are rotation pairs m0 = (col % 128) / 2 and m0 + 1: angle = pos[row][pc]
         // * freq (pc, freq per (j, t) here; the position per row in the loop).
-        const char* const gl = area + C::BM * PN_SLOTS * 4 + C::BM * C::WGN * 4;
+        const char* const gl = area + C::BM * PN_SLOTS * 4 + PN_RED<C, EPI>;
         const float* const pl = reinterpret_cast<const float*>(gl + C::BN * 4);
         float frq[EPI == E_ROPE ? TJ : 1][2];
         int pcol[EPI == E_ROPE ? TJ : 1][2];
@@ -869,7 +882,7 @@ RF_DEV void engine_epilogue(const EngineArgs& p, int m0, int n0, const f32x4 (&a
                 }
                 if (lane < 16) {
 #pragma unroll
-                    for (int i = 0; i < TI; ++i) lds_st_f32(red + (wn * C::BM + wm * C::MW + i * 16 + rl) * 4, ssr[i]);
+                    for (int i = 0; i < TI; ++i) lds_st_f32(red_at(wn, wm * C::MW + i * 16 + rl), ssr[i]);
                 }
                 lds_sync();
                 // destination row block and slot: the producer's [row][PN_SLOTS] (slot = column tile), or the
@@ -892,7 +905,7 @@ RF_DEV void engine_epilogue(const EngineArgs& p, int m0, int n0, const f32x4 (&a
                     if (row < p.m) {
                         float s = 0.f;
 #pragma unroll
-                        for (int w = 0; w < C::WGN; ++w) s += lds_ld_f32(red + (w * C::BM + t) * 4);
+                        for (int w = 0; w < C::WGN; ++w) s += lds_ld_f32(red_at(w, t));
                         float* dst = base + (int64_t)row * ld;
                         dst[slot] = s;
                         if (slot == 0)
@@ -930,22 +943,37 @@ constexpr int REGION = 16384;  // 128 rows x 64 k x 2 B
 // BM = 256: regions RA0, RA1, RB0, RB1; BM = 128 (wave tile 64 x 64): RA, RB0, RB1.  BM = 96 / 64 (wave tile
 // 48 / 32 x 64; the short tiles of the N = 1,024 projections): the same three regions with a BM-row RA that
 // only waves 0..BM/16-1 stage (the others skip it and count fewer LDS-DMA in their waits)
+// BM = 288 (wave tile 144 x 64, 9 A fragments cut 5 + 4: 20 / 20 / 16 / 16 MFMAs a phase; one round of tiles where
+// M x N just exceeds a round of 256 x 256 ones): RA0 = A rows {0-63, 144-207} and RA1 = {80-143, 224-287} are
+// 8 pieces each as at BM = 256; the other two m0 pieces (rows 64-79, 208-223) are a fifth region RAX that only
+// waves 0 and 4 stage, right after RA0 (those two count 10 LDS-DMA a K-tile in their waits, the others 8)
 template <int BM>
 struct Cfg {
-    static constexpr int NREG = BM == 256 ? 4 : 3;
-    static constexpr int NA = BM == 256 ? 2 : 1;  // A regions come first
+    static constexpr int NREG = BM >= 256 ? 4 : 3;
+    static constexpr int NA = BM >= 256 ? 2 : 1;  // A regions come first
+    static constexpr int NX = BM == 288 ? 1 : 0;  // RAX (region index NREG)
     static constexpr int A_IMG = BM * 128;        // [2 k-halves][BM rows][64 B]
     static constexpr int TILE = A_IMG + 256 * 128;
     static constexpr int LDS = 2 * TILE;
     static constexpr int MI = BM / 32;  // 16-row M fragments per wave
-    static constexpr int GLDS = 2 * NREG;  // LDS-DMA per lane per K-tile
-    static constexpr int FA = BM == 256 ? 4 : BM / 32;  // A fragments per wave per phase (rows / 16)
-    static_assert(BM == 256 || BM == 128 || BM == 96 || BM == 64, "phased tile height");
+    static constexpr int GLDS = 2 * NREG;  // LDS-DMA per lane per K-tile (waves with RAX: + 2)
+    static constexpr int FA = BM == 288 ? 5 : BM == 256 ? 4 : BM / 32;  // A fragments per wave of the m0 phases (rows / 16)
+    static constexpr int FA1 = BM == 288 ? 4 : BM == 256 ? 4 : 0;       // ... of the m1 phases
+    static_assert(BM == 288 || BM == 256 || BM == 128 || BM == 96 || BM == 64, "phased tile height");
+    static_assert(BM < 256 || FA + FA1 == MI, "m0 + m1 fragments");
 };
 // tile row of region row j (0..127); runs of 16 consecutive j map to 16 consecutive rows
 template <int BM>
 RF_DEV int region_row(int r, int j) {
-    if constexpr (BM == 256) {
+    if constexpr (BM == 288) {
+        switch (r) {
+            case 0: return j < 64 ? j : j + 80;
+            case 1: return j < 64 ? j + 80 : j + 160;
+            case 2: return (j >> 5) * 64 + (j & 31);
+            case 3: return (j >> 5) * 64 + 32 + (j & 31);
+            default: return (j < 64 ? 64 : 208) + (j & 15);  // RAX: wave 0's piece, wave 4's piece
+        }
+    } else if constexpr (BM == 256) {
         switch (r) {
             case 0: return j < 64 ? j : j + 64;
             case 1: return j < 64 ? j + 64 : j + 128;
@@ -970,25 +998,29 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
                             f32x4 (&acc)[BM / 32][4], bool pre = false) {
     using namespace ph;
     using G = Cfg<BM>;
-    constexpr int NREG = G::NREG, NA = G::NA, MI = G::MI;
+    constexpr int NREG = G::NREG, NA = G::NA, NX = G::NX, MI = G::MI;
     static_assert(NTERM == 1 || NTERM == P_F16, "phased loop: single-term operands");
-    constexpr int FA = G::FA;
+    static_assert(!(GATHER && NX), "gathered A: no RAX region");
+    constexpr int FA = G::FA, FA1 = G::FA1;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int wr = wave >> 2, wc = wave & 3;
     const int nk = kend - kbeg;  // K-tiles of this call; local tile t is global K-tile kbeg + t
     // BM < 128: only waves 0..BM/16-1 stage the A region (wave-uniform)
     const bool has_a = BM >= 128 || __builtin_amdgcn_readfirstlane(wave) < BM / 16;
+    // BM = 288: only waves 0 and 4 stage RAX (wave-uniform)
+    const bool has_x = NX && (__builtin_amdgcn_readfirstlane(wave) & 3) == 0;
 
     // ---- DMA geometry: wave w fills region rows 16 w .. 16 w + 15 (both k-halves) of each region
     const int jrow = 16 * wave + (lane >> 2);
-    int trow[NREG], grow[NREG];  // this lane's tile row; first tile row of the wave's 16-row piece (wave-uniform)
-    const bf16_t* src[NREG];
+    int trow[NREG + NX], grow[NREG + NX];  // this lane's tile row; first tile row of the wave's 16-row piece (wave-uniform)
+    const bf16_t* src[NREG + NX];
 #pragma unroll
-    for (int r = 0; r < NREG; ++r) {
+    for (int r = 0; r < NREG + NX; ++r) {
         trow[r] = region_row<BM>(r, jrow);
         grow[r] = region_row<BM>(r, 16 * wave);
     }
+    if constexpr (NX) src[NREG] = p.a + (int64_t)min(m0 + trow[NREG], p.m - 1) * p.lda;
     int am[NA], gi[NA], gy[NA], gx[NA];  // A rows (gathered for convolutions)
 #pragma unroll
     for (int r = 0; r < NA; ++r) {
@@ -1009,8 +1041,9 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
 
     // issue region r of K-tile kt into buffer kt & 1 (2 LDS-DMA per lane: the two 32-deep k-halves)
     auto issue = [&](int kt, int r) {
-        const bool is_a = r < NA;
+        const bool is_a = r < NA || r >= NREG;
         if (is_a && !has_a) return;
+        if (r >= NREG && !has_x) return;
         char* base = smem + (kt & 1) * G::TILE + (is_a ? 0 : G::A_IMG);
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh) {
@@ -1019,7 +1052,7 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
             const int k0 = (kbeg + kt) * BK2 + kh * 32;
             const bf16_t* g = src[r] + k0 + ch * 8;
             if constexpr (GATHER) {
-                if (is_a) {
+                if (r < NA) {
                     const int tap = udiv_m(k0, p.cin_m), cb = k0 - tap * p.cin_pad;
                     const int ky = udiv_m(tap, p.kw_m), kx = tap - ky * p.kw;
                     const int iy = gy[r] + ky, ix = gx[r] + kx;
@@ -1043,12 +1076,13 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
 
     const int frow = lane & 15, fch = lane >> 4;  // fragment lane geometry (16x16x32: 16 rows x 4 chunks)
     bf16x8 fa[FA][2], fb0[2][2], fb1[2][2];       // A: FA frags (16 FA rows) x 2 k-slices; B(n0), B(n1): 2 x 2
-    auto read_a = [&](const char* buf, int mi) {
+    auto read_a = [&](const char* buf, int mi) {  // (mi = 1: the FA1 fragments after the FA of mi = 0)
 #pragma unroll
         for (int i = 0; i < FA; ++i)
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                fa[i][s] = *reinterpret_cast<const bf16x8*>(buf + img<BM>(wr * (BM / 2) + mi * 64 + i * 16 + frow, s, fch));
+                if (i < (mi ? FA1 : FA))
+                    fa[i][s] = *reinterpret_cast<const bf16x8*>(buf + img<BM>(wr * (BM / 2) + mi * (FA * 16) + i * 16 + frow, s, fch));
     };
     auto read_b = [&](const char* buf, int ni, bf16x8 (&fb)[2][2]) {
 #pragma unroll
@@ -1065,6 +1099,7 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
             for (int i = 0; i < FA; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
+                    if (i >= (mi ? FA1 : FA)) continue;
                     f32x4& c = acc[mi * FA + i][ni * 2 + j];
                     if constexpr (NTERM == P_F16)
                         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fb[j][s]),
@@ -1087,18 +1122,24 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
     };
 
     // prologue: tile 0 and (BM = 256) all of tile 1 / (BM = 128) tile 1 minus RB1 in flight; wait for tile 0
-    constexpr int AHEAD = BM == 256 ? 8 : 4;  // LDS-DMA of tile 1 issued here (and of tile t+2 at a tile's wait)
+    constexpr int AHEAD = BM >= 256 ? 8 : 4;  // LDS-DMA of tile 1 issued here (and of tile t+2 at a tile's wait)
+    // BM >= 256: all but the newest K-tile's LDS-DMA of this wave have landed
+    auto wait_ahead = [&]() {
+        if (has_x) wait_vm<AHEAD + 2>();
+        else wait_vm<AHEAD>();
+    };
     // (pre: the caller already issued K-tiles 0 and 1 of this call, in this order - phased_issue01)
     if (!pre) {
 #pragma unroll
-        for (int r = 0; r < NREG; ++r) issue(0, r);
+        for (int r = 0; r < NREG + NX; ++r) issue(0, r);
     }
     if (nk > 1) {
         if (!pre) {
 #pragma unroll
-            for (int r = 0; r < (BM == 256 ? NREG : 2); ++r) issue(1, r);
+            for (int r = 0; r < (BM >= 256 ? NREG + NX : 2); ++r) issue(1, r);
         }
-        if (has_a) wait_vm<AHEAD>();
+        if (BM >= 256) wait_ahead();
+        else if (has_a) wait_vm<AHEAD>();
         else wait_vm<AHEAD - 2>();  // (BM < 128, no RA: RB0 of tile 1 only)
     } else {
         wait_vm<0>();
@@ -1112,7 +1153,7 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
     for (int t = 0; t < nk; ++t) {
         const char* buf = smem + (t & 1) * G::TILE;
         const bool pf = t + 2 < nk;
-        if constexpr (BM == 256) {
+        if constexpr (BM >= 256) {
             // phase 0: q0 = (m0, n0)
             read_b(buf, 0, fb0);
             read_a(buf, 0);
@@ -1123,6 +1164,7 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
             read_b(buf, 1, fb1);
             if (pf) {
                 issue(t + 2, 0);
+                if constexpr (NX) issue(t + 2, NREG);
                 issue(t + 2, 2);
             }
             sync_in();
@@ -1137,7 +1179,7 @@ RF_DEV void phased_mainloop(const EngineArgs& p, char* smem, int m0, int n0, int
             // phase 3: q3 = (m1, n0), no reads; RA1 free; publish tile t+1
             if (pf) {
                 issue(t + 2, 1);
-                wait_vm<8>();
+                wait_ahead();
             } else {
                 wait_vm<0>();
             }
@@ -1375,6 +1417,7 @@ __global__ __launch_bounds__(512, 1) void phased3_kernel(EngineArgs p) {
 template <int BM, int EPI, int NTERM, bool GATHER>
 __global__ __launch_bounds__(512, 1) void phased_kernel(EngineArgs p) {
     using TE = Tile<BM, 256, 2, 4, 4>;
+    static_assert(ph::Cfg<BM>::LDS + PN_AREA<TE, EPI> <= 160 * 1024, "phased tile: over the CU's 160 KiB of LDS");
     __shared__ __attribute__((aligned(16))) char smem[ph::Cfg<BM>::LDS + PN_AREA<TE, EPI>];
     if (gated_off(p)) return;
     const int tiles_m = (p.m + BM - 1) / BM;
@@ -3167,6 +3210,7 @@ int sk_grid(int m, int n, int k) {
 enum TileCode : int {
     TC_R128 = 128,         // ring 128x128, 4 waves, 3 stages: the default and every code's fall-through
     TC_P256 = 256,         // phased 256x256; without use_phased the ring's 256x256 (8 waves, 4 stages)
+    TC_P288 = 288,         // phased 288x256 (wave tile 144x64)
     TC_R64 = 642,          // ring 64x256, 8 waves
     TC_P64 = 643,          // phased 64x256
     TC_R64w4 = 644,        // ring 64x256, 4 waves
@@ -3197,6 +3241,8 @@ enum TileCode : int {
 // A launch of T tiles takes ceil(T / (256 x slots)) rounds of `fixed + per_k * K/1024 (+ add)` us each, where
 // `add` is the residual epilogue's cost (C tile read up front + fp32 store):
 //   256   phased 256x256, 2 buffers     11.0 + 20.4   add 5
+//   288   phased 288x256, 2 buffers     22.5 + 22.1   add 5    (M = 5,649, N = 3,072: 240 tiles = one round;
+//         profiles/p288_study.txt: per_k from K = 4,096 against 1,024 at N = 1,024, fixed from the full one-round grid)
 //   1282  phased 128x256, 2 buffers      2.3 + 18.4   add 5
 //   964   phased  96x256, 3 buffers      6.0 + 14.4   add 5    (M = 5,649, N = 1,024: 236 tiles = one round)
 //   645   phased  64x256, 3 buffers      6.5 + 11.8   add 5    (M = 4,096, N = 1,024: 256 tiles)
@@ -3226,6 +3272,7 @@ int pick_cfg(int m, int n, int k, int epilogue = RF_EPI_BF16) {
     if (n % 256 == 0) consider(TC_R96, cost(96, 256, 1, 2.2, 16.5, 13.0));
     if (phased) {
         consider(TC_P256, cost(256, 256, 1, 11.0, 20.4, 5.0));
+        consider(TC_P288, cost(288, 256, 1, 22.5, 22.1, 5.0));
         consider(TC_P128, cost(128, 256, 1, 2.3, 18.4, 5.0));
         consider(TC_P3_96, cost(96, 256, 1, 6.0, 14.4, 5.0));
         consider(TC_P3_64, cost(64, 256, 1, 6.5, 11.8, 5.0));
@@ -3662,6 +3709,7 @@ using TileTable = Rows<
     //  code            loop                              preconditions        fp16
     Row<TC_P256,        Phased<256>,                      PRE_PHASED,          true>,
     Row<TC_P128,        Phased<128>,                      PRE_PHASED,          true>,
+    Row<TC_P288,        Phased<288>,                      PRE_PHASED,          true>,
     Row<TC_P256,        Ring<T256>,                       PRE_N256,            false>,
     Row<TC_R128s4,      Ring<Tile<128, 128, 2, 2, 4>>,    PRE_NONE,            false>,
     Row<TC_R128s5,      Ring<Tile<128, 128, 2, 2, 5>>,    PRE_NONE,            false>,
@@ -3942,7 +3990,8 @@ extern "C" int rf_gemm_rownorm(const void* a, int64_t lda, const void* w, int64_
 }
 
 // rf_gemm_qk_rope (rf.h): the q/k/v projection with the attention's q/k norm weight and rotary encoding in the
-// epilogue (E_ROPE) on the engine's 96x256 or 8-wave 128x128 tile (the tiles the cost model picks for these shapes).
+// epilogue (E_ROPE) on the phased 288x256 tile or the engine's 96x256 or 8-wave 128x128 tile (the tiles the cost model
+// picks for these shapes).
 template <class C, int NT>
 static int launch_rope(EngineArgs p, void* stream) {
     return launch<C, E_ROPE, NT>(p, stream, "rf_gemm_qk_rope");
@@ -3987,6 +4036,10 @@ extern "C" int rf_gemm_qk_rope(const void* a, int64_t lda, const void* w, int64_
     p.rope_qscale = q_scale;
     const bool f16 = operand_dtype == RF_DT_F16;
     const int cfg = pick_cfg(m, n, k, RF_EPI_BF16);
+    if (cfg == TC_P288 && use_phased(n, k)) {  // the phased 288x256 tile (else, as in the tile table, it falls through)
+        return f16 ? launch_phased<E_ROPE, P_F16, false, 288>(p, stream, "rf_gemm_qk_rope")
+                   : launch_phased<E_ROPE, 1, false, 288>(p, stream, "rf_gemm_qk_rope");
+    }
     const bool t96 = n % 256 == 0 && cfg != TC_R128w8k2;  // (K % 64 == 0 is required above)
     if (t96) return f16 ? launch_rope<T96x256, P_F16>(p, stream) : launch_rope<T96x256, 1>(p, stream);
     return f16 ? launch_rope<T128w8k2s4, P_F16>(p, stream) : launch_rope<T128w8k2s4, 1>(p, stream);
