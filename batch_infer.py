@@ -2,6 +2,7 @@
 
     python batch_infer.py --h5_folder DIR [--batch_size 8] [--padding_length N] [--num_workers 0]
                           [--output_dir DIR] [--save_video] + the infer.py model flags
+                          (--resolution, --height / --width for rectangular frames, ...)
 
 Scenes are read with renderformer_amd.h5io in natural-sort order (`batch_infer.py:19-21`),
 padded to `--padding_length` with an explicit mask when given (`:36-45`), batched by
@@ -31,7 +32,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from infer import PRECISION, add_common_args, load_pipeline, save_views
+from infer import PRECISION, add_common_args, frame_resolution, load_pipeline, save_views
 from renderformer_amd.h5io import File
 from renderformer_amd.parallel import assign_units, scene_cost
 
@@ -311,7 +312,7 @@ def render_batches(pipeline, files, batches, args, pipelined=True):
     -> side-stream H2D -> render on the current stream -> side-stream D2H into pinned memory; batch i is
     yielded (and its files written by the caller) while batch i+1 renders and batch i+2 loads."""
     dev = pipeline.device
-    kw = dict(resolution=args.resolution, torch_dtype=PRECISION[args.precision])
+    kw = dict(resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision])
 
     model = getattr(pipeline, "model", None)
     resolve = getattr(pipeline, "resolve", None)
@@ -450,7 +451,7 @@ def main(argv=None, pipeline=None):
         costs = []
         for p in files:
             with File(p) as f:
-                costs.append(scene_cost(cfg, f["triangles"].shape[0], f["c2w"].shape[0], args.resolution))
+                costs.append(scene_cost(cfg, f["triangles"].shape[0], f["c2w"].shape[0], frame_resolution(args)))
         mine = assign_units(costs, world)[rank]
     else:
         mine = list(range(len(files)))

@@ -32,6 +32,8 @@
  *   rf_vn_encode       NeRFEncoding (nerf_encoding.py:63-84) on vertex normals, renderformer.py:139
  *   rf_ray_tokens      RayGenerator (ray_generator.py:13-50) + patchify rearrange (view_transformer.py:104-105)
  *   rf_patchify_rays   the patchify rearrange alone, for RenderFormer.forward callers (renderformer.py:171)
+ *   rf_ray_tokens_hw / rf_patchify_rays_hw  the same two for a rectangular h x w frame (fov = vertical field of
+ *                      view of the frame height; ViewTransformer.forward takes any H x W, view_transformer.py:104-105)
  *   rf_scene_pos       trans_to_cam_coord (transform.py:7-27) + process_tri_vpos_list (renderformer.py:103-124)
  *   rf_embed           token assembly renderformer.py:139-163, view_transformer.py:108 (RMSNorm eps=None)
  *   rf_hdr_output      ELU(1e-3) (view_transformer.py:86,122) + 10^x - 1 + permute (rendering_pipeline.py:119-123)
@@ -73,7 +75,8 @@ extern "C" {
 #define RF_ERR_DEVICE 4       /* an earlier launch reported a device-side error (see rf_device_error) */
 
 /* Still 16 with rf_scene_kv and rf_decoder_desc.kv_all / ld_kv_all: a new symbol and two trailing descriptor fields
- * that a zero-initialised caller leaves NULL / 0 (= the behaviour before them); nothing that existed changed. */
+ * that a zero-initialised caller leaves NULL / 0 (= the behaviour before them); nothing that existed changed.
+ * Still 16 with rf_ray_tokens_hw / rf_patchify_rays_hw: two new symbols. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -388,6 +391,19 @@ int rf_ray_tokens_dt(const float* c2w, const float* fov_deg, int n_views, int re
 int rf_patchify_rays(const float* rays_d, int n_views, int res, int patch, void* out, void* stream);
 /* rf_patchify_rays with out written as out_dtype (RF_DT_BF16 / RF_DT_F16). */
 int rf_patchify_rays_dt(const float* rays_d, int n_views, int res, int patch, void* out, int out_dtype,
+                        void* stream);
+
+/* Rectangular frames.  rf_ray_tokens_dt for an h x w frame: fov_deg is the VERTICAL field of view of the full frame
+ * height, f = h / 2 / tan(fov / 2) pixels, cx = w / 2, cy = h / 2, pixel centres at +0.5, directions
+ * ((x - cx) / f, -(y - cy) / f, -1) rotated by c2w and L2-normalised (ray_generator.py:31-48 with H != W; a horizontal
+ * fov converts as fov_v = 2 atan(tan(fov_h / 2) h / w)).  Tokens are row-major over the (h / patch) x (w / patch)
+ * patch grid: out[view * R + py * (w / patch) + px, c*patch*patch + p1*patch + p2] with R = (h / patch) (w / patch).
+ * Needs h % patch == 0, w % patch == 0 and h * w < 2^31.  The square entry points above are this one with
+ * h = w = res. */
+int rf_ray_tokens_hw(const float* c2w, const float* fov_deg, int n_views, int h, int w, int patch, void* out,
+                     float* ray_pos, int out_dtype, void* stream);
+/* rf_patchify_rays_dt for rays_d f32 [n_views, h, w, 3]: the token layout of rf_ray_tokens_hw. */
+int rf_patchify_rays_hw(const float* rays_d, int n_views, int h, int w, int patch, void* out, int out_dtype,
                         void* stream);
 
 /* Triangle positions for RoPE.  tris f32 [*, 9]; valid_idx int32 [sum n_b] (rows into tris, grouped by

@@ -1,15 +1,17 @@
 """Single-scene CLI, flag-compatible with the reference `infer.py:34-41`.
 
     python infer.py --h5_file scene.h5 [--model_id DIR|NAME] [--precision bf16|fp16|fp32]
-                    [--resolution 512] [--output_dir DIR] [--tone_mapper none]
-                    [--synthetic_seed S]
+                    [--resolution 512] [--height H] [--width W] [--output_dir DIR]
+                    [--tone_mapper none] [--synthetic_seed S]
 
 Reads the HDF5 scene with renderformer_amd.h5io (no h5py), renders every view on the HIP
 device and writes `{base}_view_{i}.exr` (linear HDR) and `{base}_view_{i}.png` (clip to
 [0, 1] x 255) like `infer.py:89-103`.  Offline additions: `--model_id` must be a local
 snapshot directory (config.json + model.safetensors) unless `--synthetic_seed` is given, in
 which case it names an architecture (e.g. renderformer-v1.1-swin-large) with deterministic
-random weights.  Tone mappers other than 'none' need the OCIO configs of `simple_ocio`,
+random weights.  `--height` / `--width` (each defaults to `--resolution`) render a
+rectangular frame, e.g. `--height 576 --width 1024`; the scene's fov is the vertical field
+of view of the frame height.  Tone mappers other than 'none' need the OCIO configs of `simple_ocio`,
 which is not available here, and are rejected.
 """
 from __future__ import annotations
@@ -32,9 +34,19 @@ def add_common_args(parser: argparse.ArgumentParser) -> None:
                         help="Local snapshot directory, or an architecture name with --synthetic_seed")
     parser.add_argument("--precision", type=str, choices=["bf16", "fp16", "fp32"], default="fp16")
     parser.add_argument("--resolution", type=int, default=512)
+    parser.add_argument("--height", type=int, default=None, help="Frame height in pixels (default: --resolution)")
+    parser.add_argument("--width", type=int, default=None, help="Frame width in pixels (default: --resolution)")
     parser.add_argument("--tone_mapper", type=str, choices=["none", "agx", "filmic", "pbr_neutral"], default="none")
     parser.add_argument("--synthetic_seed", type=int, default=None,
                         help="(offline) random-init weights of the named architecture")
+
+
+def frame_resolution(args):
+    """The pipeline's ``resolution`` for the parsed flags: --height / --width, each defaulting to --resolution; a
+    square frame stays the reference's int."""
+    h = args.resolution if args.height is None else args.height
+    w = args.resolution if args.width is None else args.width
+    return h if h == w else (h, w)
 
 
 def load_pipeline(args) -> RenderFormerRenderingPipeline:
@@ -85,7 +97,7 @@ def main(argv=None):
     c2w = data["c2w"].unsqueeze(0).to(dev)
     fov = data["fov"].unsqueeze(0).unsqueeze(-1).to(dev)
     imgs = pipeline(triangles=triangles, texture=texture, mask=mask, vn=vn, c2w=c2w, fov=fov,
-                    resolution=args.resolution, torch_dtype=PRECISION[args.precision])
+                    resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision])
     pipeline.resolve(imgs)  # the frame's fp16 range check (re-rendered in place if it overflowed) before reading it
     print("Inference completed. Rendered images shape:", imgs.shape)
     output_dir = args.output_dir if args.output_dir else os.path.dirname(os.path.abspath(args.h5_file))

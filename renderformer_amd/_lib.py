@@ -71,6 +71,8 @@ SIGNATURES = {
     "rf_vn_encode_dt": [_P, _L, _P, _I, _P, _L, _I, _P],
     "rf_ray_tokens_dt": [_P, _P, _I, _I, _I, _P, _P, _I, _P],
     "rf_patchify_rays_dt": [_P, _I, _I, _I, _P, _I, _P],
+    "rf_ray_tokens_hw": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P],
+    "rf_patchify_rays_hw": [_P, _I, _I, _I, _I, _P, _I, _P],
     "rf_ray_tokens": [_P, _P, _I, _I, _I, _P, _P, _P],
     "rf_patchify_rays": [_P, _I, _I, _I, _P, _P],
     "rf_scene_pos": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _L, _P],

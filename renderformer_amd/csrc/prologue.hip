@@ -153,23 +153,26 @@ __global__ __launch_bounds__(256) void vn_encode_kernel(const float* __restrict_
 }
 
 // ----------------------------------------------------------------------------- rays
-// RayGenerator (ray_generator.py:31-50) + rearrange 'b (h p1) (w p2) c -> b (h w) (c p1 p2)'
+// RayGenerator (ray_generator.py:31-50) + rearrange 'b (h1 p1) (w1 p2) c -> b (h1 w1) (c p1 p2)' for an h x w frame:
+// fov is the vertical field of view of the full frame height (f = h / 2 / tan(fov / 2), cx = w / 2, cy = h / 2), which
+// for h == w is the reference's formula operation for operation (the square entry points pass h = w = res).
 __global__ __launch_bounds__(256) void ray_tokens_kernel(const float* __restrict__ c2w, const float* __restrict__ fov,
-                                                         int res, int patch, bf16_t* __restrict__ out,
+                                                         int h, int w, int patch, bf16_t* __restrict__ out,
                                                          float* __restrict__ ray_pos, int f16) {
     const int view = blockIdx.y;
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned upix = blockIdx.x * blockDim.x + threadIdx.x;  // (h * w < 2^31: the last block's tail still fits)
     const float* m = c2w + view * 16;
-    if (pix == 0 && ray_pos) {
+    if (upix == 0 && ray_pos) {
         for (int c = 0; c < 9; ++c) ray_pos[view * 9 + c] = m[(c % 3) * 4 + 3];
     }
-    if (pix >= res * res) return;
-    const int y = pix / res, x = pix % res;
+    if (upix >= (unsigned)(h * w)) return;
+    const int pix = (int)upix;
+    const int y = pix / w, x = pix % w;
     const float fov_rad = fov[view] / 180.0f * 3.14159265358979323846f;
-    const float f = (float)res / 2.0f / tanf(0.5f * fov_rad);
-    const float c = (float)res / 2.0f;
-    const float dx = ((float)x + 0.5f - c) / f;
-    const float dy = -(((float)y + 0.5f - c) / f);
+    const float f = (float)h / 2.0f / tanf(0.5f * fov_rad);
+    const float cx = (float)w / 2.0f, cy = (float)h / 2.0f;
+    const float dx = ((float)x + 0.5f - cx) / f;
+    const float dy = -(((float)y + 0.5f - cy) / f);
     const float dz = -1.0f;
     float r0 = dx * m[0] + dy * m[1] + dz * m[2];
     float r1 = dx * m[4] + dy * m[5] + dz * m[6];
@@ -178,27 +181,28 @@ __global__ __launch_bounds__(256) void ray_tokens_kernel(const float* __restrict
     r0 /= nrm;
     r1 /= nrm;
     r2 /= nrm;
-    const int pw = res / patch;
+    const int ph = h / patch, pw = w / patch;
     const int tok = (y / patch) * pw + (x / patch);
     const int pp = patch * patch;
     const int feat = (y % patch) * patch + (x % patch);
-    bf16_t* o = out + ((int64_t)view * pw * pw + tok) * (3 * pp);
+    bf16_t* o = out + ((int64_t)view * ph * pw + tok) * (3 * pp);
     o[feat] = f32_to_16(r0, f16);
     o[pp + feat] = f32_to_16(r1, f16);
     o[2 * pp + feat] = f32_to_16(r2, f16);
 }
 
-__global__ __launch_bounds__(256) void patchify_rays_kernel(const float* __restrict__ rays, int res, int patch,
+__global__ __launch_bounds__(256) void patchify_rays_kernel(const float* __restrict__ rays, int h, int w, int patch,
                                                             bf16_t* __restrict__ out, int f16) {
     const int view = blockIdx.y;
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= res * res) return;
-    const int y = pix / res, x = pix % res;
-    const float* r = rays + ((int64_t)view * res * res + pix) * 3;
-    const int pw = res / patch, pp = patch * patch;
+    const unsigned upix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (upix >= (unsigned)(h * w)) return;
+    const int pix = (int)upix;
+    const int y = pix / w, x = pix % w;
+    const float* r = rays + ((int64_t)view * h * w + pix) * 3;
+    const int ph = h / patch, pw = w / patch, pp = patch * patch;
     const int tok = (y / patch) * pw + (x / patch);
     const int feat = (y % patch) * patch + (x % patch);
-    bf16_t* o = out + ((int64_t)view * pw * pw + tok) * (3 * pp);
+    bf16_t* o = out + ((int64_t)view * ph * pw + tok) * (3 * pp);
     o[feat] = f32_to_16(r[0], f16);
     o[pp + feat] = f32_to_16(r[1], f16);
     o[2 * pp + feat] = f32_to_16(r[2], f16);
@@ -412,37 +416,58 @@ extern "C" int rf_vn_encode(const float* vn, int64_t n_rows, const int32_t* dst_
     return rf_vn_encode_dt(vn, n_rows, dst_row, n_freqs, out, ldo, RF_DT_BF16, stream);
 }
 
-extern "C" int rf_ray_tokens_dt(const float* c2w, const float* fov_deg, int n_views, int res, int patch, void* out,
-                                float* ray_pos, int out_dtype, void* stream) {
+// the frame checks of the four ray entry points: both sides whole patches, pixel index in an int
+static int ray_frame_ok(const char* fn, int h, int w, int patch) {
+    RF_REQUIRE(patch > 0 && h > 0 && w > 0, "%s: need positive h, w and patch (got %d x %d, patch %d)", fn, h, w, patch);
+    RF_REQUIRE(h % patch == 0, "%s: height %d not divisible by patch %d", fn, h, patch);
+    RF_REQUIRE(w % patch == 0, "%s: width %d not divisible by patch %d", fn, w, patch);
+    RF_REQUIRE((int64_t)h * w < (1ll << 31), "%s: %d x %d pixels do not fit a 32-bit index", fn, h, w);
+    return RF_OK;
+}
+
+extern "C" int rf_ray_tokens_hw(const float* c2w, const float* fov_deg, int n_views, int h, int w, int patch,
+                                void* out, float* ray_pos, int out_dtype, void* stream) {
     RF_REQUIRE(c2w && fov_deg && out, "rf_ray_tokens: null pointer");
-    RF_REQUIRE(res % patch == 0, "rf_ray_tokens: resolution %d not divisible by patch %d", res, patch);
+    if (int rc = ray_frame_ok("rf_ray_tokens", h, w, patch)) return rc;
     RF_REQUIRE(out_dtype == RF_DT_BF16 || out_dtype == RF_DT_F16, "rf_ray_tokens: bad out_dtype");
+    RF_REQUIRE(n_views <= 65535, "rf_ray_tokens: at most 65535 views per call");
     if (n_views <= 0) return RF_OK;
-    dim3 grid((res * res + 255) / 256, n_views);
-    RF_LAUNCH(ray_tokens_kernel, grid, dim3(256), 0, (hipStream_t)stream, c2w, fov_deg, res, patch,
+    dim3 grid((unsigned)(((int64_t)h * w + 255) / 256), n_views);
+    RF_LAUNCH(ray_tokens_kernel, grid, dim3(256), 0, (hipStream_t)stream, c2w, fov_deg, h, w, patch,
                        (bf16_t*)out, ray_pos, (int)(out_dtype == RF_DT_F16));
     return rf::check_launch("rf_ray_tokens");
 }
 
-extern "C" int rf_ray_tokens(const float* c2w, const float* fov_deg, int n_views, int res, int patch, void* out,
-                             float* ray_pos, void* stream) {
-    return rf_ray_tokens_dt(c2w, fov_deg, n_views, res, patch, out, ray_pos, RF_DT_BF16, stream);
+extern "C" int rf_ray_tokens_dt(const float* c2w, const float* fov_deg, int n_views, int res, int patch, void* out,
+                                float* ray_pos, int out_dtype, void* stream) {
+    return rf_ray_tokens_hw(c2w, fov_deg, n_views, res, res, patch, out, ray_pos, out_dtype, stream);
 }
 
-extern "C" int rf_patchify_rays_dt(const float* rays_d, int n_views, int res, int patch, void* out, int out_dtype,
-                                   void* stream) {
+extern "C" int rf_ray_tokens(const float* c2w, const float* fov_deg, int n_views, int res, int patch, void* out,
+                             float* ray_pos, void* stream) {
+    return rf_ray_tokens_hw(c2w, fov_deg, n_views, res, res, patch, out, ray_pos, RF_DT_BF16, stream);
+}
+
+extern "C" int rf_patchify_rays_hw(const float* rays_d, int n_views, int h, int w, int patch, void* out,
+                                   int out_dtype, void* stream) {
     RF_REQUIRE(rays_d && out, "rf_patchify_rays: null pointer");
-    RF_REQUIRE(res % patch == 0, "rf_patchify_rays: resolution %d not divisible by patch %d", res, patch);
+    if (int rc = ray_frame_ok("rf_patchify_rays", h, w, patch)) return rc;
     RF_REQUIRE(out_dtype == RF_DT_BF16 || out_dtype == RF_DT_F16, "rf_patchify_rays: bad out_dtype");
+    RF_REQUIRE(n_views <= 65535, "rf_patchify_rays: at most 65535 views per call");
     if (n_views <= 0) return RF_OK;
-    dim3 grid((res * res + 255) / 256, n_views);
-    RF_LAUNCH(patchify_rays_kernel, grid, dim3(256), 0, (hipStream_t)stream, rays_d, res, patch, (bf16_t*)out,
+    dim3 grid((unsigned)(((int64_t)h * w + 255) / 256), n_views);
+    RF_LAUNCH(patchify_rays_kernel, grid, dim3(256), 0, (hipStream_t)stream, rays_d, h, w, patch, (bf16_t*)out,
               (int)(out_dtype == RF_DT_F16));
     return rf::check_launch("rf_patchify_rays");
 }
 
+extern "C" int rf_patchify_rays_dt(const float* rays_d, int n_views, int res, int patch, void* out, int out_dtype,
+                                   void* stream) {
+    return rf_patchify_rays_hw(rays_d, n_views, res, res, patch, out, out_dtype, stream);
+}
+
 extern "C" int rf_patchify_rays(const float* rays_d, int n_views, int res, int patch, void* out, void* stream) {
-    return rf_patchify_rays_dt(rays_d, n_views, res, patch, out, RF_DT_BF16, stream);
+    return rf_patchify_rays_hw(rays_d, n_views, res, res, patch, out, RF_DT_BF16, stream);
 }
 
 extern "C" int rf_scene_pos(const float* tris, const int32_t* valid_idx, const int32_t* scene_off, const float* c2w,

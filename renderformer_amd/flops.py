@@ -2,6 +2,8 @@
 PV over valid tokens only).  Used by bench.py for roofline fractions."""
 from __future__ import annotations
 
+from typing import Tuple
+
 from .config import RenderFormerConfig
 
 
@@ -21,10 +23,20 @@ def stage2_layer_flops(cfg: RenderFormerConfig, s: int, r: int, views: int = 1) 
     return out
 
 
-def dpt_flops(cfg: RenderFormerConfig, res: int) -> int:
+def frame_hw(resolution) -> Tuple[int, int]:
+    """``resolution`` as (height, width): an int r means the square (r, r)."""
+    if isinstance(resolution, (tuple, list)):
+        if len(resolution) != 2:
+            raise ValueError(f"resolution must be an int or (height, width), got {resolution!r}")
+        return int(resolution[0]), int(resolution[1])
+    return int(resolution), int(resolution)
+
+
+def dpt_flops(cfg: RenderFormerConfig, res) -> int:
+    """DPT head on one ``res`` = int | (height, width) frame: hp * wp tokens, height * width pixels."""
     p = cfg.patch_size
-    hp = res // p
-    r = hp * hp
+    h, w = frame_hw(res)
+    r = (h // p) * (w // p)
     d, ft, c = cfg.view_transformer_latent_dim, cfg.dpt_features, list(cfg.dpt_out_channels)
     px = [16 * r, 4 * r, r, r // 4]  # pyramid level pixel counts
     tot = sum(2 * r * d * ci for ci in c)
@@ -35,14 +47,15 @@ def dpt_flops(cfg: RenderFormerConfig, res: int) -> int:
     tot += conv(4, px[2]) + 2 * px[1] * ft * ft
     tot += conv(4, px[1]) + 2 * px[0] * ft * ft
     tot += conv(4, px[0]) + 2 * (4 * px[0]) * ft * ft
-    tot += 2 * res * res * ft * (ft // 2) * 9 + 2 * res * res * (ft // 2) * 32 * 9 + 2 * res * res * 32 * 3
+    tot += 2 * h * w * ft * (ft // 2) * 9 + 2 * h * w * (ft // 2) * 32 * 9 + 2 * h * w * 32 * 3
     return tot
 
 
-def frame_flops(cfg: RenderFormerConfig, n_tris: int, res: int, views: int = 1) -> dict:
-    """Per scene with `views` views; divide by views for per-frame numbers."""
+def frame_flops(cfg: RenderFormerConfig, n_tris: int, res, views: int = 1) -> dict:
+    """Per scene with `views` views of ``res`` = int | (height, width) pixels; divide by views for per-frame numbers."""
     s = n_tris + cfg.num_register_tokens
-    r = (res // cfg.patch_size) ** 2
+    h, w = frame_hw(res)
+    r = (h // cfg.patch_size) * (w // cfg.patch_size)
     kt = cfg.texture_channels * cfg.texture_encode_patch_size ** 2
     st1 = stage1_layer_flops(cfg, s)
     st2 = stage2_layer_flops(cfg, s, r, views)

@@ -8,7 +8,7 @@ tri_vpos_view_tf, tf32_view_tf=False)``.
 
 Execution model: every scene is *unpadded* into a packed token
 matrix — stage 1 holds ``16 + n_b`` rows per scene (register tokens then the
-valid triangles), stage 2 ``R = (res/8)^2`` ray-token rows per (scene, view).
+valid triangles), stage 2 ``R = (H/8) (W/8)`` ray-token rows per (scene, view) of an H x W frame.
 All GEMMs run over the packed rows of the whole batch at once; attention
 kernels receive per-problem row ranges.  The residual streams are fp32; the
 projection GEMMs take fp16 operands (RMSNorm / SwiGLU / attention outputs and
@@ -30,7 +30,7 @@ import math
 import os
 import threading
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -203,7 +203,8 @@ class _Plan:
     """Packed-row bookkeeping for one batch (built once per mask pattern / view count / resolution)."""
     B: int
     V: int
-    res: int
+    H: int                     # frame height and width in pixels (hp x wp patches)
+    W: int
     counts: List[int]
     T_tri: int
     T1: int
@@ -229,8 +230,21 @@ class _Plan:
     view_off: Optional[torch.Tensor] = None
 
 
-def _build_plan(mask_host, V: int, res: int, patch: int, n_reg: int, device, n_heads: int = 0) -> _Plan:
-    """The plan from a HOST copy of the mask (numpy bool [B, N]): every index table is built with numpy and reaches
+def frame_size(cfg: RenderFormerConfig, resolution) -> Tuple[int, int]:
+    """``resolution`` (an int r = the square (r, r), or (height, width)) as (H, W), checked per side: each must be
+    a positive multiple of the patch size (times the Swin window when the view transformer uses Swin attention)."""
+    H, W = ops.frame_hw(resolution)
+    unit = cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)
+    for side, n in (("height", H), ("width", W)):
+        if n <= 0 or n % unit != 0:
+            raise ValueError(f"resolution {H} x {W}: {side} {n} incompatible with patch/window size (must be a "
+                             f"positive multiple of {unit})")
+    return H, W
+
+
+def _build_plan(mask_host, V: int, res, patch: int, n_reg: int, device, n_heads: int = 0) -> _Plan:
+    """The plan of an H x W frame (``res``: (H, W), or an int for a square) from a HOST copy of the mask (numpy bool
+    [B, N]): every index table is built with numpy and reaches
     the device in ONE pinned, non-blocking copy (plus one for the two stream-K range tables), so building a plan
     never waits for the device (the frames queued before it keep running).  Only a device-only mask needs a
     read-back first (RenderFormer._plan: like flash_attn's unpad_input)."""
@@ -248,7 +262,8 @@ def _build_plan(mask_host, V: int, res: int, patch: int, n_reg: int, device, n_h
     reg_rows = np.concatenate([np.arange(cu1[b], cu1[b] + n_reg) for b in range(B)] or [np.zeros(0)])
     prob1 = [[int(cu1[b]), S[b], int(cu1[b]), S[b], int(cu1[b])] for b in range(B)]
     scene_off = np.concatenate([[0], np.cumsum(counts)])
-    hp = wp = res // patch
+    H, W = ops.frame_hw(res)
+    hp, wp = H // patch, W // patch
     R = hp * wp
     P = B * V
     kv_off, kv_src, prob2, prob_self = [0], [], [], []
@@ -269,7 +284,9 @@ def _build_plan(mask_host, V: int, res: int, patch: int, n_reg: int, device, n_h
     buf = np.empty(max(o, 1), dtype=np.int32)
     for k, a in parts.items():
         buf[offs[k][0]:offs[k][0] + offs[k][1]] = a
-    dbuf = torch.from_numpy(buf).pin_memory().to(device, non_blocking=True)
+    dbuf = torch.from_numpy(buf)
+    if torch.device(device).type == "cuda":  # (a host plan, device "cpu", only lays the tables out: the CPU tests)
+        dbuf = dbuf.pin_memory().to(device, non_blocking=True)
     t = {k: dbuf[a:a + n] for k, (a, n) in offs.items()}
     sched1 = sched2 = None
     if n_heads and ops.attn_schedule_enabled():
@@ -277,7 +294,7 @@ def _build_plan(mask_host, V: int, res: int, patch: int, n_reg: int, device, n_h
         sc = np.concatenate([ops.attn_schedule_host(prob1, n_heads, grid), ops.attn_schedule_host(prob2, n_heads, grid)])
         dsc = torch.from_numpy(sc).pin_memory().to(device, non_blocking=True)
         sched1, sched2 = dsc[:grid + 1], dsc[grid + 1:]
-    return _Plan(B=B, V=V, res=res, counts=counts, T_tri=T_tri, T1=int(cu1[-1]), T_kv=kv_off[-1], R=R, hp=hp, wp=wp,
+    return _Plan(B=B, V=V, H=H, W=W, counts=counts, T_tri=T_tri, T1=int(cu1[-1]), T_kv=kv_off[-1], R=R, hp=hp, wp=wp,
                  max_s=max(S), valid_flat=t["valid_flat"], dst_row=t["dst_row"], tri_rows=t["tri_rows"],
                  reg_rows=t["reg_rows"], scene_off=t["scene_off"], cu1=t["cu1"], kv_off=t["kv_off"],
                  kv_src_rows=t["kv_src_rows"], prob1=t["prob1"].view(-1, 5), prob2=t["prob2"].view(-1, 5),
@@ -420,7 +437,7 @@ class RenderFormer:
         # texture encoder fast path for to_h5-format textures (proven per call on the device; RF_TEX_FAST=0
         # forces the general pack + GEMM path)
         self._tex_fast = os.environ.get("RF_TEX_FAST", "1") != "0"
-        # (id(mask), V, res) -> (mask object, mask version, plan): the no-read-back fast path for a mask tensor seen
+        # (id(mask), V, (H, W)) -> (mask object, mask version, plan): the no-read-back fast path for a mask tensor seen
         # before (bench.py c4 cycles 64 fixed device masks; a view-chunked render alternates two chunk sizes)
         self._last_plan: Dict = {}
         self._host_masks: Dict = {}  # id(device mask) -> (mask, version, host copy): plan_hint
@@ -503,6 +520,7 @@ class RenderFormer:
         # the same mask tensor object, unmodified since it was planned (torch's version counter): reuse that plan
         # without reading the mask back (the host sync stalls the queue at the start of every frame).  The
         # reference is held, so the object (and its storage) cannot be recycled under the same id.
+        res = ops.frame_hw(res)
         ko = (id(mask), V, res)
         last = self._last_plan.get(ko)
         if last is not None and last[0] is mask and last[1] == mask._version:
@@ -521,6 +539,7 @@ class RenderFormer:
 
     def _plan_host(self, host, V, res):
         """The plan of a host mask (numpy bool [B, N]) from the cache keyed by its pattern: no device read-back."""
+        res = ops.frame_hw(res)
         key = (tuple(host.shape), host.tobytes(), V, res)
         plan = self._plans.get(key)
         if plan is None:
@@ -842,13 +861,15 @@ class RenderFormer:
 
     # ------------------------------------------------------------------ entry points
     @torch.no_grad()
-    def render_views(self, triangles, texture, mask, vn, c2w, fov, resolution: int, log_encode: bool = True,
+    def render_views(self, triangles, texture, mask, vn, c2w, fov, resolution, log_encode: bool = True,
                      timings: Optional[dict] = None) -> torch.Tensor:
-        """Pipeline fast path: rays, camera transform and positions are generated on the device.
-        Returns [B, V, res, res, C] linear HDR (log-decoded unless use_ldr).
+        """Pipeline fast path: rays, camera transform and positions are generated on the device.  ``resolution`` is
+        an int (a square frame) or (height, width); ``fov`` is the vertical field of view of the frame height.
+        Returns [B, V, H, W, C] linear HDR (log-decoded unless use_ldr).
 
         Every launch goes to the current stream of the MODEL's device, whatever device is current in the
         caller (the reference's own infer.py places the model on cuda:1, infer.py:43)."""
+        resolution = frame_size(self.config, resolution)
         self._require()
         with torch.cuda.device(self._device):
             # the replay (an fp16 overflow's re-render) must not log-encode the texture a second time
@@ -971,12 +992,14 @@ class RenderFormer:
             self._encode(sc, False)
 
     @torch.no_grad()
-    def render_encoded(self, scene: EncodedScene, c2w, fov, resolution: int) -> torch.Tensor:
+    def render_encoded(self, scene: EncodedScene, c2w, fov, resolution) -> torch.Tensor:
         """Render the cameras ``c2w`` [B, V, 4, 4] / ``fov`` [B, V, ...] of an encoded batch of scenes: stage 2 +
-        DPT only, per chunk of ``view_chunk`` views like ``render_views``.  Returns [B, V, res, res, C] linear HDR,
+        DPT only, per chunk of ``view_chunk`` views like ``render_views``.  ``resolution`` is an int or (height,
+        width) as in ``render_views``.  Returns [B, V, H, W, C] linear HDR,
         bit-identical to ``render_views`` of the same inputs.  Same range-check modes as ``render_views`` (``resolve
         (out)`` works); after an fp16 overflow, here or in any other render of the model, the handle is encoded
         again with the model's new operands before the frame is (re-)rendered."""
+        resolution = frame_size(self.config, resolution)
         self._require()
         self._check_handle(scene)
         with torch.cuda.device(self._device):
@@ -992,8 +1015,7 @@ class RenderFormer:
         B, V = c2w.shape[:2]
         if B != sc.batch_size:
             raise ValueError(f"c2w has batch size {B}, the encoded scene {sc.batch_size}")
-        if resolution % (cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)) != 0:
-            raise ValueError(f"resolution {resolution} incompatible with patch/window size")
+        H, W = resolution  # (frame_size checked it)
         self._refresh(sc)
         with sc.lock:
             x1, kv_all, tris, ev, st = sc.x1, sc.kv_all, sc.tris, sc.event, sc.stream
@@ -1009,7 +1031,7 @@ class RenderFormer:
             v1 = min(V, v0 + chunk)
             plan = self._plan_host(sc.mask_host, v1 - v0, resolution)
             o = self._views(plan, x1, tris, c2w[:, v0:v1], fov[:, v0:v1], resolution, kv_all)
-            o = o.view(B, v1 - v0, resolution, resolution, -1)
+            o = o.view(B, v1 - v0, H, W, -1)
             if v1 - v0 == V:
                 return o
             if out is None:
@@ -1216,8 +1238,7 @@ class RenderFormer:
                      (fov, "fov")):
             if t.device != dev:
                 raise ValueError(f"{n} must be on {dev} (got {t.device})")
-        if resolution % (cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)) != 0:
-            raise ValueError(f"resolution {resolution} incompatible with patch/window size")
+        H, W = resolution  # (frame_size checked it)
         # views in chunks of at most view_chunk (stage 1 once): every chunk runs the same launch sequence on the
         # same problem tables whatever the other views are, so a view's image does not depend on how the views of
         # a scene are batched or split over ranks (bench.py c5)
@@ -1230,13 +1251,13 @@ class RenderFormer:
                       max(plan.counts))
         x1 = self._stage1(plan, x1, pos1)
         if chunk == V:
-            return self._views(plan, x1, tris, c2w, fov, resolution).view(B, V, resolution, resolution, -1)
+            return self._views(plan, x1, tris, c2w, fov, resolution).view(B, V, H, W, -1)
         out = None
         for v0 in range(0, V, chunk):
             v1 = min(V, v0 + chunk)
             pc = plan if v1 - v0 == chunk else self._plan(mask, v1 - v0, resolution)
             o = self._views(pc, x1, tris, c2w[:, v0:v1], fov[:, v0:v1], resolution)
-            o = o.view(B, v1 - v0, resolution, resolution, -1)
+            o = o.view(B, v1 - v0, H, W, -1)
             if out is None:
                 out = torch.empty(B, V, *o.shape[2:], dtype=o.dtype, device=dev)
             out[:, v0:v1] = o
@@ -1266,7 +1287,8 @@ class RenderFormer:
     @torch.no_grad()
     def forward(self, tri_vpos_list, texture_patch_list, valid_mask, vns, rays_o, rays_d, tri_vpos_view_tf,
                 tf32_view_tf=False):
-        """Reference signature (renderformer.py:171-206).  Returns ELU'd log-space images [B, V, C, H, W]."""
+        """Reference signature (renderformer.py:171-206).  ``rays_d`` is [B, V, H, W, 3] for any valid H x W
+        (frame_size), as the reference's ViewTransformer takes it.  Returns ELU'd log-space images [B, V, C, H, W]."""
         self._require()
         with torch.cuda.device(self._device):
             args = (tri_vpos_list, texture_patch_list, valid_mask, vns, rays_o, rays_d, tri_vpos_view_tf)
@@ -1275,8 +1297,8 @@ class RenderFormer:
     def _forward(self, tri_vpos_list, texture_patch_list, valid_mask, vns, rays_o, rays_d, tri_vpos_view_tf):
         cfg, dev = self.config, self._device
         B, V = rays_o.shape[:2]
-        res = rays_d.shape[2]
-        plan = self._plan(valid_mask, V, res)
+        H, W = frame_size(cfg, tuple(rays_d.shape[2:4]))
+        plan = self._plan(valid_mask, V, (H, W))
         tris = tri_vpos_list.reshape(B, -1, 9).float().contiguous()
         x1 = self._embed_triangles(plan, texture_patch_list.float().contiguous(),
                                    vns.reshape(B, -1, 9).float().contiguous(), log_encode=False)
@@ -1286,7 +1308,7 @@ class RenderFormer:
         x1 = self._stage1(plan, x1, pos1)
         P = B * V
         ray_in = torch.empty(P * plan.R, 3 * cfg.patch_size ** 2, dtype=self._w.half, device=dev)
-        ops.patchify_rays(rays_d.reshape(P, res, res, 3).float().contiguous(), cfg.patch_size, ray_in)
+        ops.patchify_rays(rays_d.reshape(P, H, W, 3).float().contiguous(), cfg.patch_size, ray_in)
         ray_pos = rays_o.reshape(P, 1, 3).float().expand(P, 3, 3).reshape(P, 9).contiguous()
         x2 = self._ray_embed(plan, ray_in)
         # per-view positions: every (b, v) is its own set over the [P*N, 9] camera-frame triangles

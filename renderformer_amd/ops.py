@@ -14,6 +14,7 @@ from typing import Optional
 import torch
 
 from ._lib import call, load, ptr, stream
+from .flops import frame_hw  # noqa: F401  (int | (height, width) -> (height, width))
 
 EPI_BF16, EPI_F32, EPI_ADD_F32, EPI_SWIGLU = 0, 1, 2, 3
 _EPI_F16, _EPI_SWIGLU_F16 = 4, 5  # rf.h: the 16-bit epilogues with an fp16 C (chosen from out.dtype)
@@ -804,22 +805,38 @@ def vn_encode(vn: torch.Tensor, dst_row: torch.Tensor, n_freqs: int, out: torch.
     return out
 
 
-def ray_tokens(c2w: torch.Tensor, fov_deg: torch.Tensor, res: int, patch: int, out: torch.Tensor,
+def _ray_out_ok(out: torch.Tensor, n_views: int, h: int, w: int, patch: int):
+    _check(patch > 0 and h > 0 and w > 0 and h % patch == 0 and w % patch == 0,
+           f"frame {h} x {w} must be whole patches of {patch}")
+    _check(out.is_cuda and out.is_contiguous() and out.numel() == n_views * h * w * 3,
+           f"ray tokens out must be contiguous [{n_views * (h // patch) * (w // patch)}, {3 * patch * patch}]")
+
+
+def ray_tokens(c2w: torch.Tensor, fov_deg: torch.Tensor, res, patch: int, out: torch.Tensor,
                ray_pos: torch.Tensor):
+    """Ray tokens of an h x w frame (rf_ray_tokens_hw); ``res`` is an int (square) or (h, w), fov vertical."""
     _dev(c2w, torch.float32, "c2w")
+    _dev(fov_deg, torch.float32, "fov_deg")
     _check(c2w.is_contiguous() and fov_deg.is_contiguous(), "c2w/fov must be contiguous")
-    call("rf_ray_tokens_dt", ptr(c2w), ptr(fov_deg), c2w.numel() // 16, res, patch, ptr(out), ptr(ray_pos), _dt(out),
-         stream())
+    h, w = frame_hw(res)
+    n = c2w.numel() // 16
+    _check(fov_deg.numel() == n, "one fov per camera")
+    _ray_out_ok(out, n, h, w, patch)
+    _check(ray_pos is None or (ray_pos.dtype == torch.float32 and ray_pos.is_contiguous() and ray_pos.numel() == 9 * n),
+           "ray_pos must be contiguous f32 [n_views, 9]")
+    call("rf_ray_tokens_hw", ptr(c2w), ptr(fov_deg), n, h, w, patch, ptr(out), ptr(ray_pos), _dt(out), stream())
     return out
 
 
 def patchify_rays(rays_d: torch.Tensor, patch: int, out: torch.Tensor):
+    """rays_d f32 [*, h, w, 3] -> the token layout of ray_tokens (rf_patchify_rays_hw)."""
     _dev(rays_d, torch.float32, "rays_d")
-    _check(rays_d.is_contiguous() and rays_d.shape[-1] == 3 and rays_d.shape[-2] == rays_d.shape[-3],
-           "rays_d must be contiguous [*, res, res, 3]")
-    res = rays_d.shape[-2]
-    call("rf_patchify_rays_dt", ptr(rays_d), rays_d.numel() // (res * res * 3), res, patch, ptr(out), _dt(out),
-         stream())
+    _check(rays_d.dim() >= 3 and rays_d.is_contiguous() and rays_d.shape[-1] == 3,
+           "rays_d must be contiguous [*, h, w, 3]")
+    h, w = rays_d.shape[-3], rays_d.shape[-2]
+    n = rays_d.numel() // (h * w * 3)
+    _ray_out_ok(out, n, h, w, patch)
+    call("rf_patchify_rays_hw", ptr(rays_d), n, h, w, patch, ptr(out), _dt(out), stream())
     return out
 
 

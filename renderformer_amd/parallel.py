@@ -18,11 +18,12 @@ import torch
 import torch.distributed as dist
 
 from .config import RenderFormerConfig
-from .flops import frame_flops
+from .flops import frame_flops, frame_hw
 
 
-def scene_cost(cfg: RenderFormerConfig, n_tris: int, n_views: int, res: int) -> float:
-    """Algorithmic FLOPs to render all views of one scene (stage 1 once, stage 2 + DPT per view)."""
+def scene_cost(cfg: RenderFormerConfig, n_tris: int, n_views: int, res) -> float:
+    """Algorithmic FLOPs to render all views of one scene (stage 1 once, stage 2 + DPT per view) at ``res`` = int |
+    (height, width)."""
     return float(frame_flops(cfg, n_tris, res, n_views)["total"])
 
 
@@ -161,18 +162,19 @@ def frame_channels(cfg: RenderFormerConfig) -> int:
 class ShardedRenderer:
     """Render a list of scenes across ranks: each rank runs the pipeline on its LPT share, then (optionally)
     all ranks receive every frame.  ``scenes`` entries are dicts of the pipeline's tensor arguments for one
-    scene (leading batch dimension 1); all scenes of one call have the same view count."""
+    scene (leading batch dimension 1); all scenes of one call have the same view count.  ``res`` is the pipeline's
+    ``resolution``: an int (square frames) or (height, width)."""
 
     def __init__(self, pipeline, rank: int = 0, world: int = 1):
         self.pipeline = pipeline
         self.rank, self.world = rank, world
 
-    def plan(self, scenes: Sequence[dict], res: int) -> List[List[int]]:
+    def plan(self, scenes: Sequence[dict], res) -> List[List[int]]:
         cfg = self.pipeline.config
         costs = [scene_cost(cfg, int(s["mask"].sum()), int(s["c2w"].shape[1]), res) for s in scenes]
         return assign_units(costs, self.world)
 
-    def _render_resolved(self, scene: dict, res: int, kw: dict) -> torch.Tensor:
+    def _render_resolved(self, scene: dict, res, kw: dict) -> torch.Tensor:
         """One pipeline render whose fp16 range check is finished before the frame is stacked or gathered (VERDICT
         r5 weak 4): a "lazy" model's re-render happens in place in ``out``, which the gather must not have copied
         yet.  A "sync" model (the default) has resolved it already; resolve then only reports."""
@@ -182,11 +184,12 @@ class ShardedRenderer:
             resolve(out)
         return out
 
-    def _frame_shape(self, n_views: int, res: int):
-        return (n_views, res, res, frame_channels(self.pipeline.config))
+    def _frame_shape(self, n_views: int, res):
+        h, w = frame_hw(res)
+        return (n_views, h, w, frame_channels(self.pipeline.config))
 
-    def render(self, scenes: Sequence[dict], res: int = 512, gather: bool = True, **kw):
-        """Scenes sharded by LPT; returns [n_scenes, V, res, res, C] on every rank (gather) or
+    def render(self, scenes: Sequence[dict], res=512, gather: bool = True, **kw):
+        """Scenes sharded by LPT; returns [n_scenes, V, H, W, C] on every rank (gather) or
         (my scene ids, my frames)."""
         if not scenes:
             raise ValueError("no scenes")
@@ -203,8 +206,8 @@ class ShardedRenderer:
             return mine, local
         return gather_frames(local, plan)
 
-    def render_views(self, scene: dict, res: int = 512, gather: bool = True, **kw):
-        """One scene, its views split across ranks (shard_views); returns [V, res, res, C] on every rank
+    def render_views(self, scene: dict, res=512, gather: bool = True, **kw):
+        """One scene, its views split across ranks (shard_views); returns [V, H, W, C] on every rank
         (gather) or (my view range, my frames)."""
         n_views = int(scene["c2w"].shape[1])
         shards = shard_views(n_views, self.world)

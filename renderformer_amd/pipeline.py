@@ -39,6 +39,7 @@ bf16 operands: a handle made before it is encoded again from its retained inputs
 from __future__ import annotations
 
 import warnings
+from typing import Tuple, Union
 
 import torch
 
@@ -84,9 +85,13 @@ class RenderFormerRenderingPipeline:
             raise ValueError("texture must be float32 (it is log-encoded in place)")
         return texture
 
-    def render(self, triangles, texture, mask, vn, c2w, fov, resolution: int = 512,
+    def render(self, triangles, texture, mask, vn, c2w, fov, resolution: Union[int, Tuple[int, int]] = 512,
                torch_dtype: torch.dtype = torch.float16):
-        """Render [bs, nv, resolution, resolution, 3] HDR images (rendering_pipeline.py:28-125)."""
+        """Render [bs, nv, H, W, 3] HDR images (rendering_pipeline.py:28-125).  ``resolution`` is an int (the
+        reference's square frame, H = W = resolution) or ``(height, width)``; each side must be a multiple of the
+        patch size (x 8 with Swin attention: 64 for the released models).  ``fov`` is the VERTICAL field of view of
+        the full frame height in degrees (for a square frame the reference's own convention); a horizontal field of
+        view converts as ``fov_v = 2 atan(tan(fov_h / 2) * H / W)``."""
         self._check_dtype(torch_dtype, stacklevel=3)
         cfg = self.config
         texture = self._texture(texture)
@@ -101,9 +106,11 @@ class RenderFormerRenderingPipeline:
         return self.model.encode_scene(triangles, self._texture(texture), mask, vn,
                                        log_encode=not self.config.use_ldr)
 
-    def render_encoded(self, scene, c2w, fov, resolution: int = 512, torch_dtype: torch.dtype = torch.float16):
-        """Render the cameras ``c2w`` [bs, nv, 4, 4] / ``fov`` of an encoded batch: [bs, nv, resolution, resolution,
-        3] HDR, bit-identical to ``render`` of the same scene and cameras, without stage 1 and the K/V projection."""
+    def render_encoded(self, scene, c2w, fov, resolution: Union[int, Tuple[int, int]] = 512,
+                       torch_dtype: torch.dtype = torch.float16):
+        """Render the cameras ``c2w`` [bs, nv, 4, 4] / ``fov`` of an encoded batch: [bs, nv, H, W, 3] HDR
+        (``resolution``: an int or ``(height, width)`` as in ``render``), bit-identical to ``render`` of the same
+        scene and cameras, without stage 1 and the K/V projection.  One handle renders any frame size."""
         self._check_dtype(torch_dtype, stacklevel=3)
         out = self.model.render_encoded(scene, c2w, fov, resolution)
         self.last_precision = {"requested": str(torch_dtype), "computed": self.model.precision}
