@@ -2902,6 +2902,148 @@ __global__ __launch_bounds__(256, 1) void conv3x3_c32_kernel(EngineArgs p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// conv3x3_hs_kernel: conv3x3_c32_kernel's chunk-per-barrier structure with the block geometry a template parameter
+// and the full conv epilogue, for the DPT levels too small for halo2 / halo3's 16 x 32 x 128 blocks to fill the chip
+// (128^2: 64 such blocks, 64^2: 16).  A block is 4 waves (one per SIMD) over a TH x TW pixel tile and BN output
+// channels; wave w owns tile rows TH / 4 * w .. + TH / 4 - 1 (TI = TH / 4 * TW / 16 pixel fragments) x all BN channels
+// (TJ = BN / 16 W fragments).  Per 32-channel chunk the (TH + 2) x (TW + 2) halo (halo2's column-keyed XOR image) and
+// the chunk's 9 W slices (9 BN / 16 one-KiB pieces) land by LDS-DMA in one of two buffers while the previous chunk
+// computes; no ordinary load runs in the loop, so hipcc leaves the counted vmcnt alone.  Blocks walk pixel
+// tile-major: the channel tiles of a pixel tile are consecutive ids (same XCD: the halo comes from L2 after the first).
+template <int TH_, int TW_, int BN_>
+struct HsCfg {
+    static constexpr int TH = TH_, TW = TW_, BN = BN_, NWAVE = 4;
+    static constexpr int HWID = TW + 2, HPIX = (TH + 2) * HWID;
+    static constexpr int HPW = ((HPIX + 15) / 16 + NWAVE - 1) / NWAVE, HPIECES = HPW * NWAVE;  // 1-KiB halo pieces
+    static constexpr int WPIECES = 9 * BN / 16, WPW = (WPIECES + NWAVE - 1) / NWAVE;          // 1-KiB W pieces
+    static constexpr int HBYTES = HPIECES * 1024, WBYTES = WPIECES * 1024, BUF = HBYTES + WBYTES, LDS = 2 * BUF;
+    static constexpr int RW = TH / NWAVE, FX = TW / 16, TI = RW * FX, TJ = BN / 16;
+    static_assert(TH % NWAVE == 0 && TW % 16 == 0 && BN % 16 == 0, "hs: whole fragments per wave");
+    static_assert(HPW + WPW <= 24 && LDS <= 160 * 1024, "hs: vmcnt range, LDS budget");
+};
+// the epilogue's view of the block: 4 waves stacked over the pixel rows, RW rows of TW pixels x BN channels each
+template <class G>
+struct HsTile {
+    static constexpr int WGN = 1, WGM = G::NWAVE, MW = G::RW * G::TW, NWD = G::BN, TI = G::TI, TJ = G::TJ;
+};
+
+template <int TH_, int TW_, int BN_>
+__global__ __launch_bounds__(256, 1) void conv3x3_hs_kernel(EngineArgs p, int tiles_n) {
+    using G = HsCfg<TH_, TW_, BN_>;
+    constexpr int TH = G::TH, TW = G::TW, HWID = G::HWID, HPIX = G::HPIX, NWAVE = G::NWAVE, HPW = G::HPW,
+                  WPIECES = G::WPIECES, WPW = G::WPW, HBYTES = G::HBYTES, BUF = G::BUF, TI = G::TI, TJ = G::TJ,
+                  FX = G::FX;
+    __shared__ __attribute__((aligned(16))) char smem[G::LDS];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nwg = gridDim.x, hw = blockIdx.x;
+    const int xcd = hw & 7, q = nwg >> 3, r = nwg & 7;
+    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (hw >> 3);
+    const int tx_n = p.wo / TW, ty_n = p.ho / TH;
+    const int tn = wg % tiles_n, pt = wg / tiles_n;
+    const int tx = pt % tx_n, rest = pt / tx_n;
+    const int ty = rest % ty_n, img = rest / ty_n;
+    const int y0 = ty * TH, x0 = tx * TW, n0 = tn * G::BN;
+    const int nch = p.cin_pad / 32;
+
+    // halo piece t of this wave = halo pixels 16 (wave + 4 t) .. + 15, 64 B each (16-B chunk ^ column key); pixels
+    // past the image or past the HPIX in use read the zero row
+    int hpix[HPW], hch[HPW];
+#pragma unroll
+    for (int t = 0; t < HPW; ++t) {
+        const int hp = (wave + NWAVE * t) * 16 + (lane >> 2);
+        hch[t] = (lane & 3) ^ h2::hkey(hp % HWID);
+        int pix = -1;
+        if (hp < HPIX) {
+            const int hy = hp / HWID, hx = hp - hy * HWID;
+            const int iy = y0 + hy - 1, ix = x0 + hx - 1;
+            if (iy >= 0 && iy < p.hi && ix >= 0 && ix < p.wi) pix = (img * p.hi + iy) * p.wi + ix;
+        }
+        hpix[t] = pix;
+    }
+    // W piece v = tap v / TJ, output channels n0 + 16 (v % TJ) .. + 15 of the [cout_pad][9][cin_pad] bank; wave w
+    // stages pieces w, w + 4, ... (wave-uniform count: WPIECES need not be a multiple of 4)
+    const int wr = lane >> 2;
+    auto issue = [&](int chunk, int buf) {
+        char* b = smem + buf * BUF;
+#pragma unroll
+        for (int t = 0; t < HPW; ++t) {
+            const bf16_t* src = hpix[t] >= 0 ? p.a + (int64_t)hpix[t] * p.cin_pad + hch[t] * 8 + chunk * 32 : p.zero;
+            __builtin_amdgcn_global_load_lds(GLB_PTR(void, src), LDS_PTR(void, b + (wave + NWAVE * t) * 1024), 16, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < WPW; ++u) {
+            const int v = wave + NWAVE * u;
+            if (WPIECES % NWAVE != 0 && v >= WPIECES) break;
+            const int tap = v / TJ, row = 16 * (v % TJ) + wr;
+            const bf16_t* src = p.w + (int64_t)(n0 + row) * p.ldw + tap * p.cin_pad + chunk * 32 + (((lane & 3) ^ ((row >> 1) & 3)) * 8);
+            __builtin_amdgcn_global_load_lds(GLB_PTR(void, src), LDS_PTR(void, b + HBYTES + v * 1024), 16, 0, 0);
+        }
+    };
+    const int n_issue = HPW + (WPIECES - wave + NWAVE - 1) / NWAVE;  // LDS-DMA per wave per chunk
+
+    f32x4 acc[TI][TJ];
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int frow = lane & 15, fch = lane >> 4;
+    // fragment i = tile row RW wave + i / FX, columns 16 (i % FX) .. + 15; at tap (ty, tx) its lane's halo pixel is
+    // row RW wave + i / FX + ty, column hx = 16 (i % FX) + frow + tx: hadr[i % FX][tx] + (i / FX + ty) HWID 64
+    uint32_t hadr[FX][3];
+#pragma unroll
+    for (int h = 0; h < FX; ++h)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int hx = 16 * h + frow + t;
+            hadr[h][t] = (uint32_t)(uintptr_t)LDS_PTR(char, smem) + ((G::RW * wave) * HWID + hx) * 64 +
+                         ((fch ^ h2::hkey(hx)) << 4);
+        }
+    const uint32_t wadr = (uint32_t)(uintptr_t)LDS_PTR(char, smem) + HBYTES + lds_off(frow, fch);
+
+    issue(0, 0);
+    for (int c = 0; c < nch; ++c) {
+        const int buf = c & 1;
+        if (c + 1 < nch) {
+            issue(c + 1, buf ^ 1);           // lands under this chunk's MFMAs
+            wait_vm_rt<HPW + WPW>(n_issue);  // this wave's pieces of chunk c landed (chunk c + 1's still in flight)
+        } else {
+            wait_vm<0>();
+        }
+        __builtin_amdgcn_s_barrier();  // every wave's pieces of chunk c landed
+        __builtin_amdgcn_sched_barrier(0);
+        const uint32_t bo = buf * BUF;
+        // one wave per SIMD: tap t + 1's fragments are read under tap t's MFMAs (two register sets)
+        bf16x8 fa[2][TI], fb[2][TJ];
+        auto rd = [&](int tap, int s) {
+#pragma unroll
+            for (int j = 0; j < TJ; ++j)
+                fb[s][j] = *LDS_PTR(const bf16x8, (uintptr_t)(wadr + bo + (tap * TJ + j) * 1024));
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+                fa[s][i] = *LDS_PTR(const bf16x8, (uintptr_t)(hadr[i % FX][tap % 3] + bo + (i / FX + tap / 3) * HWID * 64));
+        };
+        rd(0, 0);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int s = tap & 1;
+            if (tap + 1 < 9) rd(tap + 1, s ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+#pragma unroll
+                for (int j = 0; j < TJ; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fb[s][j]),
+                                                                       __builtin_bit_cast(f16x8, fa[s][i]), acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();  // buffer `buf` is free for chunk c + 2
+    }
+    engine_epilogue<HsTile<G>, E_CONV, TW, false>(p, (img * p.ho + y0) * p.wo + x0, n0, acc);
+}
+
 #ifdef RF_STUDY  // conv3x3_hk_kernel (measured slower than halo3): study build only
 // ---------------------------------------------------------------------------------------------------
 // conv3x3_hk_kernel: the chunk-per-barrier structure of conv3x3_c32_kernel for 3x3 / stride 1 / pad 1 fp16
@@ -4220,6 +4362,59 @@ static int launch_hk(EngineArgs a, void* stream, const char* what) {
 #endif
 }
 
+// conv3x3_hs_kernel serves the non-final 3x3 / stride 1 / pad 1 fp16 convolutions with a multiple of 32 filters
+// whose image is too small for halo2 / halo3's blocks to fill the chip (RF_CONV_HALO_SMALL=0: the gathered engine
+// launches instead; 1, the default: the largest block geometry that still makes >= 256 blocks, else the smallest;
+// a geometry code below: that geometry wherever the image admits it).  An explicit RF_CONV_TILE keeps its kernel.
+enum HsGeom : int { HS_NONE = 0, HS_16x32x64 = 163264, HS_16x32x32 = 163232, HS_8x16x64 = 81664, HS_8x16x32 = 81632 };
+struct HsChoice {
+    int code, th, tw, bn;
+};
+static constexpr HsChoice HS_GEOMS[] = {  // largest block first
+    {HS_16x32x64, 16, 32, 64}, {HS_16x32x32, 16, 32, 32}, {HS_8x16x64, 8, 16, 64}, {HS_8x16x32, 8, 16, 32}};
+static int64_t hs_blocks(const EngineArgs& a, const HsChoice& g) {  // 0: the geometry does not admit the launch
+    if (a.ho % g.th || a.wo % g.tw || a.cout % g.bn) return 0;
+    return (int64_t)(a.m / (g.th * g.tw)) * (a.cout / g.bn);
+}
+static int hs_pick(const EngineArgs& a) {
+    const int env = rf::env_int("RF_CONV_HALO_SMALL", 1);
+    if (env == 0 || (a.flags & RF_CONV_FINAL) || a.deconv || a.m <= 0) return HS_NONE;
+    if (!rf::env_set("RF_CONV_HALO_SMALL") && rf::env_set("RF_CONV_TILE")) return HS_NONE;
+    if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return HS_NONE;
+    if (a.cin_pad % 32 || a.cout % 32 || a.cout > a.n) return HS_NONE;
+    // halo2 / halo3's shapes stay theirs, whichever knob decides between them and the engine
+    if (a.ho % h2::TH == 0 && a.wo % h2::TW == 0 && (a.n % 128 == 0 || a.n == 64) &&
+        (int64_t)(a.m / 512) * (a.n == 64 ? 1 : a.n / 128) >= 256)
+        return HS_NONE;
+    if (env != 1) {
+        for (const HsChoice& g : HS_GEOMS)
+            if (g.code == env) return hs_blocks(a, g) ? g.code : HS_NONE;
+        return HS_NONE;
+    }
+    int code = HS_NONE;
+    for (const HsChoice& g : HS_GEOMS) {
+        const int64_t blocks = hs_blocks(a, g);
+        if (blocks) code = g.code;
+        if (blocks >= 256) break;
+    }
+    return code;
+}
+
+template <int TH, int TW, int BN>
+static int launch_hs_t(const EngineArgs& a, void* stream, const char* what) {
+    const int tiles_n = a.cout / BN;
+    const int nwg = (a.m / (TH * TW)) * tiles_n;
+    RF_LAUNCH((conv3x3_hs_kernel<TH, TW, BN>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, tiles_n);
+    return rf::check_launch(what);
+}
+
+static int launch_hs(const EngineArgs& a, int code, void* stream, const char* what) {
+    if (code == HS_16x32x64) return launch_hs_t<16, 32, 64>(a, stream, what);
+    if (code == HS_16x32x32) return launch_hs_t<16, 32, 32>(a, stream, what);
+    if (code == HS_8x16x64) return launch_hs_t<8, 16, 64>(a, stream, what);
+    return launch_hs_t<8, 16, 32>(a, stream, what);
+}
+
 // Conv tile codes: what RF_CONV_TILE=<number> forces (tests and tools/kbench.py pass these numbers); unset = CT_AUTO,
 // the heuristics of conv_common / conv_f16_dp.  Unrelated to the dense GEMM's RF_GEMM_TILE codes.
 enum ConvTile : int {
@@ -4333,6 +4528,11 @@ static int conv_common(EngineArgs& p, int nterm, bool gather, const void* w_hi, 
     // keeping >= 8 K-steps.
     int64_t skg = 0;
     int ct = conv_tile_env();
+    // images too small for the 16 x 32 x 128 halo blocks: the right-sized halo kernel, ahead of the small-level
+    // tiles and the stream-K split below (all gathered engine launches)
+    if (nterm == P_F16 && gather && !hk_ok(p) && !halo3_ok(p) && !halo2_ok(p)) {
+        if (const int hs = hs_pick(p)) return launch_hs(p, hs, stream, what);
+    }
     // small DPT levels (<= 4,096 output pixels per launch: the 64^2 / 32^2 refinenets and their rn convs): the
     // 64x64 tile, data-parallel at K <= 2,304 and stream-K above (GPU time per launch, rocprofv3 over
     // tools/kbench.py conv: 256->256 @32 32.4 -> 26.6 us, @64 30.1 -> 27.6 us, 1024->256 @32 50.4 -> 41.4 us;

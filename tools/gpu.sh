@@ -8,7 +8,8 @@
 #   prof [bench args]  rocprofv3 kernel-trace stats of a short bench run
 #   trace            kernel + HIP API + memory-copy trace of a 2-frame bench run (no counters)
 #   attn             attention GPU tests, ablation timings, per-segment stamps
-#   ab "<envA>" "<envB>"   the bench twice under each of two env settings, interleaved
+#   ab "<envA>" "<envB>"   the bench twice (AB_RUNS times) under each of two env settings, interleaved; AB_ARGS adds
+#                    bench.py arguments (e.g. "--steps 20 --warmup 5")
 #   kb <mode>...     tools/kbench.py micro-benchmarks (KB_* env passed through)
 #   configs          the other SURVEY 8d configurations (bunny, 1024^2, 4 views, 4 scenes, v1-base 256^2)
 #   c5               config 5 (24 views at 1024^2), bf16 and MX fp8
@@ -70,9 +71,9 @@ attn)
     timeout -k 10 300 python tools/attn_ablate.py > $O/ablate.log 2>&1
     timeout -k 10 120 python tools/attn_ablate.py stamps 32 > $O/stamps.log 2>&1 ;;
 ab)
-    for i in 1 2; do
-        env $1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_a$i.json 2>> $O/bench.err
-        env $2 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_b$i.json 2>> $O/bench.err
+    for i in $(seq ${AB_RUNS:-2}); do
+        env $1 timeout -k 10 300 python bench.py --no-cpu-baseline $AB_ARGS > $O/bench_a$i.json 2>> $O/bench.err
+        env $2 timeout -k 10 300 python bench.py --no-cpu-baseline $AB_ARGS > $O/bench_b$i.json 2>> $O/bench.err
     done ;;
 kb)
     for W in "$@"; do timeout -k 10 400 python -u tools/kbench.py $W > $O/kb_$W.log 2>&1; done ;;

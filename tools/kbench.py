@@ -187,6 +187,8 @@ def conv():
     for f16 in (True,) if os.environ.get("KB_F16_ONLY") else (True, False):
         shapes = [(256, 256, 256), (256, 128, 512), (256, 256, 128), (256, 256, 64), (256, 256, 32),
                   (128, 256, 256), (128, 32, 512), (512, 256, 128), (1024, 256, 64), (1024, 256, 32)]
+        if os.environ.get("KB_CONV_SHAPES"):  # "cin,cout,hw;..." instead of the list above
+            shapes = [tuple(int(v) for v in x.split(",")) for x in os.environ["KB_CONV_SHAPES"].split(";")]
         if os.environ.get("KB_CONV_HW"):  # only these output resolutions
             shapes = [x for x in shapes if str(x[2]) in os.environ["KB_CONV_HW"].split(",")]
         for cin, cout, hw in shapes:
@@ -206,7 +208,13 @@ def conv():
                 os.environ["RF_CONV_H2S"] = t[4:] if t.startswith("h2s") else "4"
                 os.environ["RF_H2_DBG"] = t[4:] if t.startswith("h2db") else "0"  # h2db1/2/3: ablations
                 os.environ["RF_CONV_HK"] = "1" if t == "hk" else "0"  # hk: conv3x3_hk_kernel (4 waves, one barrier per chunk)
-                if not t.startswith("auto") and not t.startswith("h2") and t != "hk" and not t.startswith("h3"):
+                # hs: conv3x3_hs_kernel (the small-image halo kernel) with the host's geometry, hs<code>: that geometry
+                # (hs163232, hs81632, ...), hs0: the knob off (the parent's launches); other labels leave the knob unset
+                if t.startswith("hs"):
+                    os.environ["RF_CONV_HALO_SMALL"] = t[2:] or "1"
+                else:
+                    os.environ.pop("RF_CONV_HALO_SMALL", None)
+                if not t.startswith("auto") and not t.startswith("h2") and t != "hk" and not t.startswith("h3") and not t.startswith("hs"):
                     os.environ["RF_CONV_TILE"] = t.replace("ph", "")
                 ms = timeit(lambda: conv(x, out_f32=True), reps=10)
                 os.environ.pop("RF_CONV_TILE", None)
