@@ -2,7 +2,8 @@
 
     python batch_infer.py --h5_folder DIR [--batch_size 8] [--padding_length N] [--num_workers 0]
                           [--output_dir DIR] [--save_video] + the infer.py model flags
-                          (--resolution, --height / --width for rectangular frames, ...)
+                          (--resolution, --height / --width for rectangular frames, --overscan for
+                          frame sizes that are no multiple of the model's frame unit, ...)
 
 Scenes are read with renderformer_amd.h5io in natural-sort order (`batch_infer.py:19-21`),
 padded to `--padding_length` with an explicit mask when given (`:36-45`), batched by
@@ -312,7 +313,9 @@ def render_batches(pipeline, files, batches, args, pipelined=True):
     -> side-stream H2D -> render on the current stream -> side-stream D2H into pinned memory; batch i is
     yielded (and its files written by the caller) while batch i+1 renders and batch i+2 loads."""
     dev = pipeline.device
-    kw = dict(resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision])
+    # (the pinned D2H slots below take the RETURNED frames' shape: the requested H x W, also under --overscan)
+    kw = dict(resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision],
+              overscan=getattr(args, "overscan", False))
 
     model = getattr(pipeline, "model", None)
     resolve = getattr(pipeline, "resolve", None)

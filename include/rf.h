@@ -34,6 +34,8 @@
  *   rf_patchify_rays   the patchify rearrange alone, for RenderFormer.forward callers (renderformer.py:171)
  *   rf_ray_tokens_hw / rf_patchify_rays_hw  the same two for a rectangular h x w frame (fov = vertical field of
  *                      view of the frame height; ViewTransformer.forward takes any H x W, view_transformer.py:104-105)
+ *   rf_ray_tokens_cam  rf_ray_tokens_hw for pinhole intrinsics (fx, fy, cx, cy) and for a token frame larger than the
+ *                      requested frame (overscan); rf_hdr_output_win / rf_frame_window write the requested window
  *   rf_scene_pos       trans_to_cam_coord (transform.py:7-27) + process_tri_vpos_list (renderformer.py:103-124)
  *   rf_embed           token assembly renderformer.py:139-163, view_transformer.py:108 (RMSNorm eps=None)
  *   rf_hdr_output      ELU(1e-3) (view_transformer.py:86,122) + 10^x - 1 + permute (rendering_pipeline.py:119-123)
@@ -76,7 +78,8 @@ extern "C" {
 
 /* Still 16 with rf_scene_kv and rf_decoder_desc.kv_all / ld_kv_all: a new symbol and two trailing descriptor fields
  * that a zero-initialised caller leaves NULL / 0 (= the behaviour before them); nothing that existed changed.
- * Still 16 with rf_ray_tokens_hw / rf_patchify_rays_hw: two new symbols. */
+ * Still 16 with rf_ray_tokens_hw / rf_patchify_rays_hw: two new symbols.
+ * Still 16 with rf_ray_tokens_cam / rf_hdr_output_win / rf_frame_window: three new symbols. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -406,6 +409,24 @@ int rf_ray_tokens_hw(const float* c2w, const float* fov_deg, int n_views, int h,
 int rf_patchify_rays_hw(const float* rays_d, int n_views, int h, int w, int patch, void* out, int out_dtype,
                         void* stream);
 
+/* Pinhole intrinsics and overscan.  rf_ray_tokens_hw for a camera given either by fov_deg [n_views] (as above) or by
+ * intr f32 [n_views, 4] = (fx, fy, cx, cy) in pixels of the REQUESTED frame_h x frame_w frame -- exactly one of the
+ * two is non-NULL -- and for a token frame h x w (the rf_ray_tokens_hw checks apply to it) that may be larger than
+ * the requested frame, which sits at rows [y0, y0 + frame_h), columns [x0, x0 + frame_w) inside it (0 <= y0,
+ * y0 + frame_h <= h, 0 <= x0, x0 + frame_w <= w).
+ * Intrinsics convention: origin at the top-left corner of the requested frame, pixel (x, y) has its centre at
+ * (x + 0.5, y + 0.5); camera-space direction ((x + 0.5 - cx) / fx, -(y + 0.5 - cy) / fy, -1), rotated by c2w and
+ * L2-normalised.  The fov convention is fx = fy = frame_h / 2 / tan(fov / 2), cx = frame_w / 2, cy = frame_h / 2, and
+ * in fov mode those are computed from frame_h / frame_w with rf_ray_tokens_hw's expressions.  Non-positive focal
+ * lengths are the caller's error (not read back, not checked).
+ * Token pixel (x, y) of the h x w frame is pixel (x - x0, y - y0) of that camera: dx = ((float)(x - x0) + 0.5f - cx) /
+ * fx, dy = -(((float)(y - y0) + 0.5f - cy) / fy), so the pixels outside the requested frame are real rays of a
+ * slightly wider view (the padded frame's principal point is (cx + x0, cy + y0)), not padding values.
+ * With h = frame_h, w = frame_w, y0 = x0 = 0 and fov_deg the output is bit-identical to rf_ray_tokens_hw.  Token layout
+ * and ray_pos as in rf_ray_tokens_hw. */
+int rf_ray_tokens_cam(const float* c2w, const float* fov_deg, const float* intr, int n_views, int frame_h, int frame_w,
+                      int h, int w, int y0, int x0, int patch, void* out, float* ray_pos, int out_dtype, void* stream);
+
 /* Triangle positions for RoPE.  tris f32 [*, 9]; valid_idx int32 [sum n_b] (rows into tris, grouped by
  * scene, offsets scene_off[B+1]).  For each set s (s = b when c2w == NULL, else s = b*n_views + v with the
  * camera transform p -> R^T (p - t)), writes n_reg centre rows then the n_b triangle rows to
@@ -427,6 +448,15 @@ int rf_embed(float* out, int64_t ldo, const int32_t* out_rows, int rows, int dim
  * [n, h, w, c] when channels_last, else [n, c, h, w]. */
 int rf_hdr_output(const float* logits, float* out, int n, int c, int h, int w, float elu_alpha, int log_decode,
                   int channels_last, void* stream);
+/* rf_hdr_output on the window rows [y0, y0 + oh), columns [x0, x0 + ow) of the h x w logits only: out is [n, oh, ow,
+ * c] when channels_last, else [n, c, oh, ow].  The per-element arithmetic is rf_hdr_output's: the full window gives
+ * its bits, any window the corresponding slice of its output.  Needs a non-empty window inside the image. */
+int rf_hdr_output_win(const float* logits, float* out, int n, int c, int h, int w, int y0, int x0, int oh, int ow,
+                      float elu_alpha, int log_decode, int channels_last, void* stream);
+/* The same window of FINISHED channels-last frames f32 [n, h, w, c] -> out [n, oh, ow, c], a copy: the crop of an
+ * overscanned frame, whose decode already ran in the epilogue of the DPT's last convolution (RF_CONV_FINAL). */
+int rf_frame_window(const float* frames, float* out, int n, int h, int w, int c, int y0, int x0, int oh, int ow,
+                    void* stream);
 
 /* DPT convolutions on the GEMM engine.  Activations are NHWC; a convolution reads its input as two
  * bf16 planes (hi = bf16(x), lo = bf16(x - hi); channel stride cin_pad, padded channels zero) and its

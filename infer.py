@@ -2,7 +2,7 @@
 
     python infer.py --h5_file scene.h5 [--model_id DIR|NAME] [--precision bf16|fp16|fp32]
                     [--resolution 512] [--height H] [--width W] [--output_dir DIR]
-                    [--tone_mapper none] [--synthetic_seed S]
+                    [--overscan] [--tone_mapper none] [--synthetic_seed S]
 
 Reads the HDF5 scene with renderformer_amd.h5io (no h5py), renders every view on the HIP
 device and writes `{base}_view_{i}.exr` (linear HDR) and `{base}_view_{i}.png` (clip to
@@ -11,7 +11,10 @@ snapshot directory (config.json + model.safetensors) unless `--synthetic_seed` i
 which case it names an architecture (e.g. renderformer-v1.1-swin-large) with deterministic
 random weights.  `--height` / `--width` (each defaults to `--resolution`) render a
 rectangular frame, e.g. `--height 576 --width 1024`; the scene's fov is the vertical field
-of view of the frame height.  Tone mappers other than 'none' need the OCIO configs of `simple_ocio`,
+of view of the frame height.  Each side must be a multiple of the model's frame unit (64 for the
+released Swin models) unless `--overscan` is given, e.g. `--height 1080 --width 1920 --overscan`:
+the padded frame (1088 rows) is rendered as a slightly wider view and the requested window
+written.  Tone mappers other than 'none' need the OCIO configs of `simple_ocio`,
 which is not available here, and are rejected.
 """
 from __future__ import annotations
@@ -36,6 +39,9 @@ def add_common_args(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--resolution", type=int, default=512)
     parser.add_argument("--height", type=int, default=None, help="Frame height in pixels (default: --resolution)")
     parser.add_argument("--width", type=int, default=None, help="Frame width in pixels (default: --resolution)")
+    parser.add_argument("--overscan", action="store_true",
+                        help="Render any frame size (e.g. --height 1080 --width 1920): the frame padded to multiples "
+                             "of the model's frame unit is rendered and the requested window returned")
     parser.add_argument("--tone_mapper", type=str, choices=["none", "agx", "filmic", "pbr_neutral"], default="none")
     parser.add_argument("--synthetic_seed", type=int, default=None,
                         help="(offline) random-init weights of the named architecture")
@@ -97,7 +103,7 @@ def main(argv=None):
     c2w = data["c2w"].unsqueeze(0).to(dev)
     fov = data["fov"].unsqueeze(0).unsqueeze(-1).to(dev)
     imgs = pipeline(triangles=triangles, texture=texture, mask=mask, vn=vn, c2w=c2w, fov=fov,
-                    resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision])
+                    resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision], overscan=args.overscan)
     pipeline.resolve(imgs)  # the frame's fp16 range check (re-rendered in place if it overflowed) before reading it
     print("Inference completed. Rendered images shape:", imgs.shape)
     output_dir = args.output_dir if args.output_dir else os.path.dirname(os.path.abspath(args.h5_file))

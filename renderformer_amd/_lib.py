@@ -73,6 +73,9 @@ SIGNATURES = {
     "rf_patchify_rays_dt": [_P, _I, _I, _I, _P, _I, _P],
     "rf_ray_tokens_hw": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P],
     "rf_patchify_rays_hw": [_P, _I, _I, _I, _I, _P, _I, _P],
+    "rf_ray_tokens_cam": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
+    "rf_hdr_output_win": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
+    "rf_frame_window": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "rf_ray_tokens": [_P, _P, _I, _I, _I, _P, _P, _P],
     "rf_patchify_rays": [_P, _I, _I, _I, _P, _P],
     "rf_scene_pos": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _L, _P],

@@ -191,6 +191,59 @@ __global__ __launch_bounds__(256) void ray_tokens_kernel(const float* __restrict
     o[2 * pp + feat] = f32_to_16(r2, f16);
 }
 
+// ray_tokens_kernel for a pinhole camera given by its intrinsics, and for a token frame (h x w) larger than the
+// requested frame (frame_h x frame_w), which sits at (y0, x0) inside it: token pixel (x, y) is pixel (x - x0, y - y0)
+// of the requested frame's camera, so the border pixels are real rays of a slightly wider view.  intr = (fx, fy, cx,
+// cy) per view in pixels of the requested frame; without it (fov mode) f, cx, cy come from frame_h / frame_w with
+// ray_tokens_kernel's expressions, and everything after dx / dy is that kernel's code: h = frame_h, w = frame_w,
+// y0 = x0 = 0 gives its bits.
+__global__ __launch_bounds__(256) void ray_tokens_cam_kernel(const float* __restrict__ c2w,
+                                                             const float* __restrict__ fov,
+                                                             const float* __restrict__ intr, int frame_h, int frame_w,
+                                                             int h, int w, int y0, int x0, int patch,
+                                                             bf16_t* __restrict__ out, float* __restrict__ ray_pos,
+                                                             int f16) {
+    const int view = blockIdx.y;
+    const unsigned upix = blockIdx.x * blockDim.x + threadIdx.x;  // (h * w < 2^31: the last block's tail still fits)
+    const float* m = c2w + view * 16;
+    if (upix == 0 && ray_pos) {
+        for (int c = 0; c < 9; ++c) ray_pos[view * 9 + c] = m[(c % 3) * 4 + 3];
+    }
+    if (upix >= (unsigned)(h * w)) return;
+    const int pix = (int)upix;
+    const int y = pix / w, x = pix % w;
+    float fx, fy, cx, cy;
+    if (intr) {
+        fx = intr[view * 4 + 0];
+        fy = intr[view * 4 + 1];
+        cx = intr[view * 4 + 2];
+        cy = intr[view * 4 + 3];
+    } else {
+        const float fov_rad = fov[view] / 180.0f * 3.14159265358979323846f;
+        fx = fy = (float)frame_h / 2.0f / tanf(0.5f * fov_rad);
+        cx = (float)frame_w / 2.0f;
+        cy = (float)frame_h / 2.0f;
+    }
+    const float dx = ((float)(x - x0) + 0.5f - cx) / fx;
+    const float dy = -(((float)(y - y0) + 0.5f - cy) / fy);
+    const float dz = -1.0f;
+    float r0 = dx * m[0] + dy * m[1] + dz * m[2];
+    float r1 = dx * m[4] + dy * m[5] + dz * m[6];
+    float r2 = dx * m[8] + dy * m[9] + dz * m[10];
+    const float nrm = fmaxf(sqrtf(r0 * r0 + r1 * r1 + r2 * r2), 1e-12f);
+    r0 /= nrm;
+    r1 /= nrm;
+    r2 /= nrm;
+    const int ph = h / patch, pw = w / patch;
+    const int tok = (y / patch) * pw + (x / patch);
+    const int pp = patch * patch;
+    const int feat = (y % patch) * patch + (x % patch);
+    bf16_t* o = out + ((int64_t)view * ph * pw + tok) * (3 * pp);
+    o[feat] = f32_to_16(r0, f16);
+    o[pp + feat] = f32_to_16(r1, f16);
+    o[2 * pp + feat] = f32_to_16(r2, f16);
+}
+
 __global__ __launch_bounds__(256) void patchify_rays_kernel(const float* __restrict__ rays, int h, int w, int patch,
                                                             bf16_t* __restrict__ out, int f16) {
     const int view = blockIdx.y;
@@ -325,6 +378,41 @@ __global__ __launch_bounds__(256) void hdr_output_kernel(const float* __restrict
     }
 }
 
+// hdr_output_kernel on the window [y0, y0 + oh) x [x0, x0 + ow) of the h x w logits: one thread per OUTPUT pixel,
+// the same per-element arithmetic, so the full window gives its bits and any window that output's slice.
+__global__ __launch_bounds__(256) void hdr_output_win_kernel(const float* __restrict__ logits, float* __restrict__ out,
+                                                             int64_t n_pix, int c, int hw, int w, int y0, int x0,
+                                                             int oh, int ow, float alpha, int log_decode,
+                                                             int channels_last) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix) return;
+    const int ohw = oh * ow;
+    const int64_t img = i / ohw, opx = i % ohw;
+    const int64_t px = (int64_t)(y0 + (int)(opx / ow)) * w + (x0 + (int)(opx % ow));
+    for (int ch = 0; ch < c; ++ch) {
+        float y = logits[(img * c + ch) * hw + px];
+        y = y > 0.f ? y : alpha * expm1f(y);
+        if (log_decode) y = powf(10.0f, y) - 1.0f;
+        out[channels_last ? i * c + ch : (img * c + ch) * ohw + opx] = y;
+    }
+}
+
+// The window [y0, y0 + oh) x [x0, x0 + ow) of finished channels-last frames [n, h, w, c] as [n, oh, ow, c]: a copy.
+// The DPT's last convolution decodes in its epilogue (gemm.hip RF_CONV_FINAL), so an overscanned frame is cropped
+// after it.  One thread per float of an output row (ow * c contiguous floats in both tensors).
+__global__ __launch_bounds__(256) void frame_window_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                           int64_t n_elems, int h, int w, int c, int y0, int x0,
+                                                           int oh, int ow) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_elems) return;
+    const int row_len = ow * c;
+    const int64_t row = i / row_len;
+    const int col = (int)(i % row_len);
+    const int64_t img = row / oh;
+    const int oy = (int)(row % oh);
+    out[i] = in[((img * h + (y0 + oy)) * w + x0) * c + col];
+}
+
 }  // namespace
 
 extern "C" int rf_texture_pack(float* texture, int64_t n_rows, int channels, int patch_elems, int log_channels,
@@ -438,6 +526,25 @@ extern "C" int rf_ray_tokens_hw(const float* c2w, const float* fov_deg, int n_vi
     return rf::check_launch("rf_ray_tokens");
 }
 
+extern "C" int rf_ray_tokens_cam(const float* c2w, const float* fov_deg, const float* intr, int n_views, int frame_h,
+                                 int frame_w, int h, int w, int y0, int x0, int patch, void* out, float* ray_pos,
+                                 int out_dtype, void* stream) {
+    RF_REQUIRE(c2w && out, "rf_ray_tokens_cam: null pointer");
+    RF_REQUIRE((fov_deg != nullptr) != (intr != nullptr), "rf_ray_tokens_cam: exactly one of fov_deg and intr");
+    if (int rc = ray_frame_ok("rf_ray_tokens_cam", h, w, patch)) return rc;
+    RF_REQUIRE(frame_h > 0 && frame_w > 0, "rf_ray_tokens_cam: need a positive frame (got %d x %d)", frame_h, frame_w);
+    RF_REQUIRE(y0 >= 0 && x0 >= 0 && (int64_t)y0 + frame_h <= h && (int64_t)x0 + frame_w <= w,
+               "rf_ray_tokens_cam: the %d x %d frame at (%d, %d) does not lie inside the %d x %d token frame", frame_h,
+               frame_w, y0, x0, h, w);
+    RF_REQUIRE(out_dtype == RF_DT_BF16 || out_dtype == RF_DT_F16, "rf_ray_tokens_cam: bad out_dtype");
+    RF_REQUIRE(n_views <= 65535, "rf_ray_tokens_cam: at most 65535 views per call");
+    if (n_views <= 0) return RF_OK;
+    dim3 grid((unsigned)(((int64_t)h * w + 255) / 256), n_views);
+    RF_LAUNCH(ray_tokens_cam_kernel, grid, dim3(256), 0, (hipStream_t)stream, c2w, fov_deg, intr, frame_h, frame_w, h,
+              w, y0, x0, patch, (bf16_t*)out, ray_pos, (int)(out_dtype == RF_DT_F16));
+    return rf::check_launch("rf_ray_tokens_cam");
+}
+
 extern "C" int rf_ray_tokens_dt(const float* c2w, const float* fov_deg, int n_views, int res, int patch, void* out,
                                 float* ray_pos, int out_dtype, void* stream) {
     return rf_ray_tokens_hw(c2w, fov_deg, n_views, res, res, patch, out, ray_pos, out_dtype, stream);
@@ -499,4 +606,37 @@ extern "C" int rf_hdr_output(const float* logits, float* out, int n, int c, int 
     RF_LAUNCH(hdr_output_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        logits, out, n_pix, c, h * w, elu_alpha, log_decode, channels_last);
     return rf::check_launch("rf_hdr_output");
+}
+
+// the window checks of the two windowed output entry points: a non-empty window inside the h x w image
+static int window_ok(const char* fn, int n, int c, int h, int w, int y0, int x0, int oh, int ow) {
+    RF_REQUIRE(n >= 0 && c > 0 && h > 0 && w > 0, "%s: need n >= 0 and positive c, h, w", fn);
+    RF_REQUIRE(oh > 0 && ow > 0 && y0 >= 0 && x0 >= 0 && (int64_t)y0 + oh <= h && (int64_t)x0 + ow <= w,
+               "%s: the %d x %d window at (%d, %d) does not lie inside the %d x %d image", fn, oh, ow, y0, x0, h, w);
+    RF_REQUIRE((int64_t)h * w < (1ll << 31) && (int64_t)ow * c < (1ll << 31), "%s: %d x %d pixels do not fit a 32-bit "
+               "index", fn, h, w);
+    RF_REQUIRE((int64_t)n * oh * ow * c < (1ll << 39), "%s: too many output elements for one launch", fn);
+    return RF_OK;
+}
+
+extern "C" int rf_hdr_output_win(const float* logits, float* out, int n, int c, int h, int w, int y0, int x0, int oh,
+                                 int ow, float elu_alpha, int log_decode, int channels_last, void* stream) {
+    RF_REQUIRE(logits && out, "rf_hdr_output_win: null pointer");
+    if (int rc = window_ok("rf_hdr_output_win", n, c, h, w, y0, x0, oh, ow)) return rc;
+    const int64_t n_pix = (int64_t)n * oh * ow;
+    if (n_pix <= 0) return RF_OK;
+    RF_LAUNCH(hdr_output_win_kernel, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
+              out, n_pix, c, h * w, w, y0, x0, oh, ow, elu_alpha, log_decode, channels_last);
+    return rf::check_launch("rf_hdr_output_win");
+}
+
+extern "C" int rf_frame_window(const float* frames, float* out, int n, int h, int w, int c, int y0, int x0, int oh,
+                               int ow, void* stream) {
+    RF_REQUIRE(frames && out, "rf_frame_window: null pointer");
+    if (int rc = window_ok("rf_frame_window", n, c, h, w, y0, x0, oh, ow)) return rc;
+    const int64_t n_elems = (int64_t)n * oh * ow * c;
+    if (n_elems <= 0) return RF_OK;
+    RF_LAUNCH(frame_window_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames,
+              out, n_elems, h, w, c, y0, x0, oh, ow);
+    return rf::check_launch("rf_frame_window");
 }

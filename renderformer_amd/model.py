@@ -242,6 +242,44 @@ def frame_size(cfg: RenderFormerConfig, resolution) -> Tuple[int, int]:
     return H, W
 
 
+def frame_layout(cfg: RenderFormerConfig, resolution, overscan: bool = False) -> Tuple[int, int, int, int, int, int]:
+    """``(H, W, Hp, Wp, y0, x0)``: the requested frame H x W, the frame Hp x Wp the model renders (what the plan, the
+    ray tokens and the DPT see) and where the requested frame sits inside it.
+
+    Without ``overscan`` this is ``frame_size`` plus zeros: Hp = H, Wp = W, and a side that is no multiple of the
+    frame unit u (the patch size, times the Swin window with Swin attention: 64 for the released models) raises.
+    With ``overscan`` any positive H x W is taken: Hp = ceil(H / u) u, Wp = ceil(W / u) u, and the requested frame is
+    centred, y0 = (Hp - H) // 2, x0 = (Wp - W) // 2 (1080 -> 1088 rows, y0 = 4).  A frame whose sides are multiples
+    of u already gives what it gives without ``overscan``."""
+    if not overscan:
+        H, W = frame_size(cfg, resolution)
+        return H, W, H, W, 0, 0
+    H, W = ops.frame_hw(resolution)
+    unit = cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)
+    for side, n in (("height", H), ("width", W)):
+        if n <= 0:
+            raise ValueError(f"resolution {H} x {W}: {side} {n} must be positive")
+    Hp, Wp = -(-H // unit) * unit, -(-W // unit) * unit
+    return H, W, Hp, Wp, (Hp - H) // 2, (Wp - W) // 2
+
+
+def _check_camera(c2w, fov, intrinsics):
+    """Exactly one of ``fov`` and ``intrinsics``; intrinsics float32 [B, V, 4] (values are not read back: a
+    non-positive focal length is the caller's error)."""
+    if (fov is None) == (intrinsics is None):
+        raise ValueError("pass exactly one of fov and intrinsics" +
+                         (" (fov may be None only with intrinsics=)" if fov is None else " (got both)"))
+    if intrinsics is None:
+        return
+    if not isinstance(intrinsics, torch.Tensor) or intrinsics.dtype != torch.float32:
+        raise ValueError("intrinsics must be a float32 tensor [B, V, 4] = (fx, fy, cx, cy) in pixels, got "
+                         f"{getattr(intrinsics, 'dtype', type(intrinsics))}")
+    want = tuple(c2w.shape[:2]) + (4,) if isinstance(c2w, torch.Tensor) and c2w.dim() == 4 else None
+    if intrinsics.dim() != 3 or intrinsics.shape[-1] != 4 or (want is not None and tuple(intrinsics.shape) != want):
+        raise ValueError(f"intrinsics must be [B, V, 4] = (fx, fy, cx, cy) per camera"
+                         f"{'' if want is None else f', here {list(want)}'}, got {list(intrinsics.shape)}")
+
+
 def _build_plan(mask_host, V: int, res, patch: int, n_reg: int, device, n_heads: int = 0) -> _Plan:
     """The plan of an H x W frame (``res``: (H, W), or an int for a square) from a HOST copy of the mask (numpy bool
     [B, N]): every index table is built with numpy and reaches
@@ -854,29 +892,50 @@ class RenderFormer:
         ops.embed(x2, None, T2, W.patch_token, 1, ray_lin, W.ray_norm, ops.FLT_EPS)
         return x2
 
-    def _decode(self, plan: _Plan, taps, log_decode: bool, channels_last: bool):
-        """DPT head + ELU(1e-3) (+ 10^x - 1) — the last two fused into the final conv."""
-        return self._w.dpt(taps, plan.B * plan.V, plan.hp, plan.wp, self.config.patch_size, 1e-3, log_decode,
-                           channels_last)
+    def _decode(self, plan: _Plan, taps, log_decode: bool, channels_last: bool, *, window=None):
+        """DPT head + ELU(1e-3) (+ 10^x - 1) — the last two fused into the final conv.  ``window`` = (y0, x0, H, W):
+        only that window of the plan's (padded) frame is returned (an overscanned frame; channels-last), as one more
+        small launch behind the final conv, whose epilogue has already decoded the pixels."""
+        out = self._w.dpt(taps, plan.B * plan.V, plan.hp, plan.wp, self.config.patch_size, 1e-3, log_decode,
+                          channels_last)
+        if window is None:
+            return out
+        if not channels_last:
+            raise ValueError("a frame window is cut from channels-last frames")
+        return ops.frame_window(out, window)
 
     # ------------------------------------------------------------------ entry points
     @torch.no_grad()
     def render_views(self, triangles, texture, mask, vn, c2w, fov, resolution, log_encode: bool = True,
-                     timings: Optional[dict] = None) -> torch.Tensor:
+                     timings: Optional[dict] = None, *, intrinsics=None, overscan: bool = False) -> torch.Tensor:
         """Pipeline fast path: rays, camera transform and positions are generated on the device.  ``resolution`` is
         an int (a square frame) or (height, width); ``fov`` is the vertical field of view of the frame height.
         Returns [B, V, H, W, C] linear HDR (log-decoded unless use_ldr).
 
+        ``intrinsics`` (instead of ``fov``, which is then None): float32 [B, V, 4] = (fx, fy, cx, cy) in pixels of
+        the requested H x W frame, origin at its top-left corner, pixel (x, y) centred at (x + 0.5, y + 0.5);
+        camera-space direction ((x + 0.5 - cx) / fx, -(y + 0.5 - cy) / fy, -1), rotated by c2w and L2-normalised.
+        The fov convention is fx = fy = H / 2 / tan(fov / 2), cx = W / 2, cy = H / 2.  Values are not read back:
+        non-positive focal lengths are the caller's error.
+
+        ``overscan=True`` takes any positive H x W (``frame_layout``): the model renders the frame padded to
+        multiples of the frame unit with the same focal lengths, the requested frame centred in it (the border
+        pixels are real rays of a slightly wider view), and only the requested window is returned.  Without it a
+        side that is no multiple of the unit raises; with it on a frame that needs no padding the call issues the
+        same launches and returns the same bits as without.
+
         Every launch goes to the current stream of the MODEL's device, whatever device is current in the
         caller (the reference's own infer.py places the model on cuda:1, infer.py:43)."""
-        resolution = frame_size(self.config, resolution)
+        layout = frame_layout(self.config, resolution, overscan)
+        _check_camera(c2w, fov, intrinsics)
         self._require()
+        cam = dict(intrinsics=intrinsics, overscan=overscan)
         with torch.cuda.device(self._device):
             # the replay (an fp16 overflow's re-render) must not log-encode the texture a second time
             return self._guarded(
-                lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, resolution, log_encode),
-                lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, resolution, False),
-                (triangles, texture, mask, vn, c2w, fov))
+                lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, layout[:2], log_encode, **cam),
+                lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, layout[:2], False, **cam),
+                (triangles, texture, mask, vn, c2w, fov if intrinsics is None else intrinsics))
 
     # ------------------------------------------------------------------ encode once, render many cameras
     @torch.no_grad()
@@ -992,30 +1051,36 @@ class RenderFormer:
             self._encode(sc, False)
 
     @torch.no_grad()
-    def render_encoded(self, scene: EncodedScene, c2w, fov, resolution) -> torch.Tensor:
+    def render_encoded(self, scene: EncodedScene, c2w, fov, resolution, *, intrinsics=None,
+                       overscan: bool = False) -> torch.Tensor:
         """Render the cameras ``c2w`` [B, V, 4, 4] / ``fov`` [B, V, ...] of an encoded batch of scenes: stage 2 +
         DPT only, per chunk of ``view_chunk`` views like ``render_views``.  ``resolution`` is an int or (height,
-        width) as in ``render_views``.  Returns [B, V, H, W, C] linear HDR,
+        width), ``intrinsics`` [B, V, 4] (with ``fov=None``) and ``overscan`` as in ``render_views``.  Returns
+        [B, V, H, W, C] linear HDR,
         bit-identical to ``render_views`` of the same inputs.  Same range-check modes as ``render_views`` (``resolve
         (out)`` works); after an fp16 overflow, here or in any other render of the model, the handle is encoded
         again with the model's new operands before the frame is (re-)rendered."""
-        resolution = frame_size(self.config, resolution)
+        layout = frame_layout(self.config, resolution, overscan)
+        _check_camera(c2w, fov, intrinsics)
         self._require()
         self._check_handle(scene)
         with torch.cuda.device(self._device):
-            run = lambda: self._render_encoded(scene, c2w, fov, resolution)  # noqa: E731
-            return self._guarded(run, run, (c2w, fov))
+            run = lambda: self._render_encoded(scene, c2w, fov, layout[:2], intrinsics=intrinsics,  # noqa: E731
+                                               overscan=overscan)
+            return self._guarded(run, run, (c2w, fov if intrinsics is None else intrinsics))
 
-    def _render_encoded(self, sc: EncodedScene, c2w, fov, resolution):
+    def _render_encoded(self, sc: EncodedScene, c2w, fov, resolution, *, intrinsics=None, overscan=False):
         cfg, dev = self.config, self._device
         self._check_handle(sc)
-        for t, n in ((c2w, "c2w"), (fov, "fov")):
+        cam, cam_name = (fov, "fov") if intrinsics is None else (intrinsics, "intrinsics")
+        for t, n in ((c2w, "c2w"), (cam, cam_name)):
             if t.device != dev:
                 raise ValueError(f"{n} must be on {dev} (got {t.device})")
         B, V = c2w.shape[:2]
         if B != sc.batch_size:
             raise ValueError(f"c2w has batch size {B}, the encoded scene {sc.batch_size}")
-        H, W = resolution  # (frame_size checked it)
+        H, W, Hp, Wp, _, _ = frame_layout(cfg, resolution, overscan)  # (the entry point checked it)
+        cut = lambda t, a, b: None if t is None else t[:, a:b]  # noqa: E731
         self._refresh(sc)
         with sc.lock:
             x1, kv_all, tris, ev, st = sc.x1, sc.kv_all, sc.tris, sc.event, sc.stream
@@ -1029,8 +1094,9 @@ class RenderFormer:
         out = None
         for v0 in range(0, V, chunk):
             v1 = min(V, v0 + chunk)
-            plan = self._plan_host(sc.mask_host, v1 - v0, resolution)
-            o = self._views(plan, x1, tris, c2w[:, v0:v1], fov[:, v0:v1], resolution, kv_all)
+            plan = self._plan_host(sc.mask_host, v1 - v0, (Hp, Wp))
+            o = self._views(plan, x1, tris, c2w[:, v0:v1], cut(fov, v0, v1), resolution, kv_all,
+                            intrinsics=cut(intrinsics, v0, v1), overscan=overscan)
             o = o.view(B, v1 - v0, H, W, -1)
             if v1 - v0 == V:
                 return o
@@ -1231,19 +1297,22 @@ class RenderFormer:
         return (f"{proj} projection operands{fp8}, bf16 attention q/k/v, fp32 accumulate/softmax/residual; DPT "
                 f"{'fp16' if self.dpt_precision == 'f16' else 'bf16x3'} operands, fp32 accumulate")
 
-    def _render_views(self, triangles, texture, mask, vn, c2w, fov, resolution, log_encode):
+    def _render_views(self, triangles, texture, mask, vn, c2w, fov, resolution, log_encode, *, intrinsics=None,
+                      overscan=False):
         cfg, dev = self.config, self._device
         B, V = c2w.shape[:2]
         for t, n in ((triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn"), (c2w, "c2w"),
-                     (fov, "fov")):
+                     (fov, "fov") if intrinsics is None else (intrinsics, "intrinsics")):
             if t.device != dev:
                 raise ValueError(f"{n} must be on {dev} (got {t.device})")
-        H, W = resolution  # (frame_size checked it)
+        H, W, Hp, Wp, _, _ = frame_layout(cfg, resolution, overscan)  # (the entry point checked it)
+        padded = (Hp, Wp)  # what the plans are built for, and cached by
+        cut = lambda t, a, b: None if t is None else t[:, a:b]  # noqa: E731
         # views in chunks of at most view_chunk (stage 1 once): every chunk runs the same launch sequence on the
         # same problem tables whatever the other views are, so a view's image does not depend on how the views of
         # a scene are batched or split over ranks (bench.py c5)
         chunk = V if not self.view_chunk else min(V, int(self.view_chunk))
-        plan = self._plan(mask, chunk, resolution)
+        plan = self._plan(mask, chunk, padded)
         tris = triangles.reshape(B, -1, 9).float().contiguous()
         x1 = self._embed_triangles(plan, texture, vn.reshape(B, -1, 9).float().contiguous(), log_encode)
         pos1 = torch.empty(plan.T1, 9, dtype=torch.float32, device=dev)
@@ -1251,24 +1320,30 @@ class RenderFormer:
                       max(plan.counts))
         x1 = self._stage1(plan, x1, pos1)
         if chunk == V:
-            return self._views(plan, x1, tris, c2w, fov, resolution).view(B, V, H, W, -1)
+            return self._views(plan, x1, tris, c2w, fov, resolution, intrinsics=intrinsics,
+                               overscan=overscan).view(B, V, H, W, -1)
         out = None
         for v0 in range(0, V, chunk):
             v1 = min(V, v0 + chunk)
-            pc = plan if v1 - v0 == chunk else self._plan(mask, v1 - v0, resolution)
-            o = self._views(pc, x1, tris, c2w[:, v0:v1], fov[:, v0:v1], resolution)
+            pc = plan if v1 - v0 == chunk else self._plan(mask, v1 - v0, padded)
+            o = self._views(pc, x1, tris, c2w[:, v0:v1], cut(fov, v0, v1), resolution,
+                            intrinsics=cut(intrinsics, v0, v1), overscan=overscan)
             o = o.view(B, v1 - v0, H, W, -1)
             if out is None:
                 out = torch.empty(B, V, *o.shape[2:], dtype=o.dtype, device=dev)
             out[:, v0:v1] = o
         return out
 
-    def _views(self, plan: _Plan, x1, tris, c2w, fov, resolution, kv_all=None):
-        """Stage 2 + DPT + decode for the plan's views of every scene (c2w [B, Vc, 4, 4], fov [B, Vc, ...]);
-        ``kv_all``: the scene's K/V of every decoder layer when it is already known (an EncodedScene's)."""
+    def _views(self, plan: _Plan, x1, tris, c2w, fov, resolution, kv_all=None, *, intrinsics=None, overscan=False):
+        """Stage 2 + DPT + decode for the plan's views of every scene (c2w [B, Vc, 4, 4], fov [B, Vc, ...] or
+        intrinsics [B, Vc, 4]); ``kv_all``: the scene's K/V of every decoder layer when it is already known (an
+        EncodedScene's).  ``resolution`` is the requested (H, W); the plan is the padded frame's (frame_layout).
+        Returns [P, H, W, C]."""
         cfg, dev = self.config, self._device
         B, V = plan.B, plan.V
         P = B * V
+        H, W, Hp, Wp, y0, x0 = frame_layout(cfg, resolution, overscan)
+        padded = (Hp, Wp) != (H, W)
         c2w_v = c2w.reshape(P, 4, 4).float().contiguous()
         eye = self._w.eyes.get(P)
         if eye is None:
@@ -1276,13 +1351,19 @@ class RenderFormer:
         rays_c2w, pos_c2w = (eye, c2w_v) if cfg.turn_to_cam_coord else (c2w_v, eye)
         ray_in = torch.empty(P * plan.R, 3 * cfg.patch_size ** 2, dtype=self._w.half, device=dev)
         ray_pos = torch.empty(P, 9, dtype=torch.float32, device=dev)
-        ops.ray_tokens(rays_c2w, fov.reshape(P).float().contiguous(), resolution, cfg.patch_size, ray_in, ray_pos)
+        if intrinsics is None and not padded:  # the plain frame keeps rf_ray_tokens_hw (the bench's launch sequence)
+            ops.ray_tokens(rays_c2w, fov.reshape(P).float().contiguous(), resolution, cfg.patch_size, ray_in, ray_pos)
+        else:
+            ops.ray_tokens_cam(rays_c2w, None if fov is None else fov.reshape(P).float().contiguous(),
+                               None if intrinsics is None else intrinsics.reshape(P, 4).contiguous(), (H, W),
+                               (Hp, Wp), (y0, x0), cfg.patch_size, ray_in, ray_pos)
         x2 = self._ray_embed(plan, ray_in)
         pos2 = torch.empty(plan.T_kv, 9, dtype=torch.float32, device=dev)
         ops.scene_pos(tris, plan.valid_flat, plan.scene_off, pos_c2w, B, V, cfg.num_register_tokens, pos2,
                       plan.kv_off, max(plan.counts))
         taps = self._stage2(plan, x2, x1, pos2, ray_pos, kv_all)
-        return self._decode(plan, taps, log_decode=not cfg.use_ldr, channels_last=True)
+        return self._decode(plan, taps, log_decode=not cfg.use_ldr, channels_last=True,
+                            window=(y0, x0, H, W) if padded else None)
 
     @torch.no_grad()
     def forward(self, tri_vpos_list, texture_patch_list, valid_mask, vns, rays_o, rays_d, tri_vpos_view_tf,

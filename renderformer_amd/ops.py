@@ -828,6 +828,35 @@ def ray_tokens(c2w: torch.Tensor, fov_deg: torch.Tensor, res, patch: int, out: t
     return out
 
 
+def ray_tokens_cam(c2w: torch.Tensor, fov_deg: Optional[torch.Tensor], intrinsics: Optional[torch.Tensor], frame,
+                   res, origin, patch: int, out: torch.Tensor, ray_pos: torch.Tensor):
+    """Ray tokens of the h x w token frame ``res`` for cameras given by ``fov_deg`` [n] or ``intrinsics`` [n, 4] =
+    (fx, fy, cx, cy) in pixels of the requested frame ``frame`` = (frame_h, frame_w), which sits at ``origin`` =
+    (y0, x0) inside the token frame (rf_ray_tokens_cam; exactly one of fov_deg / intrinsics)."""
+    _dev(c2w, torch.float32, "c2w")
+    _check((fov_deg is None) != (intrinsics is None), "exactly one of fov_deg and intrinsics")
+    _check(c2w.is_contiguous(), "c2w must be contiguous")
+    n = c2w.numel() // 16
+    if fov_deg is not None:
+        _dev(fov_deg, torch.float32, "fov_deg")
+        _check(fov_deg.is_contiguous() and fov_deg.numel() == n, "one contiguous fov per camera")
+    else:
+        _dev(intrinsics, torch.float32, "intrinsics")
+        _check(intrinsics.is_contiguous() and intrinsics.numel() == 4 * n and intrinsics.shape[-1] == 4,
+               "intrinsics must be contiguous [n_views, 4]: (fx, fy, cx, cy) per camera")
+    fh, fw = frame_hw(frame)
+    h, w = frame_hw(res)
+    y0, x0 = (int(v) for v in origin)
+    _check(fh > 0 and fw > 0 and y0 >= 0 and x0 >= 0 and y0 + fh <= h and x0 + fw <= w,
+           f"the {fh} x {fw} frame at ({y0}, {x0}) must lie inside the {h} x {w} token frame")
+    _ray_out_ok(out, n, h, w, patch)
+    _check(ray_pos is None or (ray_pos.dtype == torch.float32 and ray_pos.is_contiguous() and ray_pos.numel() == 9 * n),
+           "ray_pos must be contiguous f32 [n_views, 9]")
+    call("rf_ray_tokens_cam", ptr(c2w), ptr(fov_deg), ptr(intrinsics), n, fh, fw, h, w, y0, x0, patch, ptr(out),
+         ptr(ray_pos), _dt(out), stream())
+    return out
+
+
 def patchify_rays(rays_d: torch.Tensor, patch: int, out: torch.Tensor):
     """rays_d f32 [*, h, w, 3] -> the token layout of ray_tokens (rf_patchify_rays_hw)."""
     _dev(rays_d, torch.float32, "rays_d")
@@ -869,4 +898,40 @@ def hdr_output(logits: torch.Tensor, out: torch.Tensor, elu_alpha: float, log_de
     _check(logits.is_contiguous() and out.is_contiguous(), "hdr_output: contiguous tensors required")
     n, c, h, w = logits.shape
     call("rf_hdr_output", ptr(logits), ptr(out), n, c, h, w, elu_alpha, int(log_decode), int(channels_last), stream())
+    return out
+
+
+def _window_ok(name: str, h: int, w: int, window):
+    y0, x0, oh, ow = (int(v) for v in window)
+    _check(oh > 0 and ow > 0 and y0 >= 0 and x0 >= 0 and y0 + oh <= h and x0 + ow <= w,
+           f"{name}: the {oh} x {ow} window at ({y0}, {x0}) must lie inside the {h} x {w} image")
+    return y0, x0, oh, ow
+
+
+def hdr_output_window(logits: torch.Tensor, out: torch.Tensor, window, elu_alpha: float, log_decode: bool,
+                      channels_last: bool = True):
+    """hdr_output on ``window`` = (y0, x0, oh, ow) of the logits [n, c, h, w] only (rf_hdr_output_win): out is
+    [n, oh, ow, c], or [n, c, oh, ow] without channels_last, and holds the corresponding slice of hdr_output's bits."""
+    _dev(logits, torch.float32, "logits")
+    _dev(out, torch.float32, "out")
+    _check(logits.dim() == 4 and logits.is_contiguous() and out.is_contiguous(),
+           "hdr_output_window: contiguous [n, c, h, w] logits and a contiguous out required")
+    n, c, h, w = logits.shape
+    y0, x0, oh, ow = _window_ok("hdr_output_window", h, w, window)
+    _check(tuple(out.shape) == ((n, oh, ow, c) if channels_last else (n, c, oh, ow)),
+           "hdr_output_window: out must be [n, oh, ow, c] (channels_last) or [n, c, oh, ow]")
+    call("rf_hdr_output_win", ptr(logits), ptr(out), n, c, h, w, y0, x0, oh, ow, elu_alpha, int(log_decode),
+         int(channels_last), stream())
+    return out
+
+
+def frame_window(frames: torch.Tensor, window) -> torch.Tensor:
+    """``window`` = (y0, x0, oh, ow) of finished channels-last frames f32 [n, h, w, c] as a new contiguous
+    [n, oh, ow, c] tensor (rf_frame_window): the crop of an overscanned frame."""
+    _dev(frames, torch.float32, "frames")
+    _check(frames.dim() == 4 and frames.is_contiguous(), "frame_window: contiguous [n, h, w, c] frames required")
+    n, h, w, c = frames.shape
+    y0, x0, oh, ow = _window_ok("frame_window", h, w, window)
+    out = torch.empty(n, oh, ow, c, dtype=torch.float32, device=frames.device)
+    call("rf_frame_window", ptr(frames), ptr(out), n, h, w, c, y0, x0, oh, ow, stream())
     return out

@@ -163,7 +163,8 @@ class ShardedRenderer:
     """Render a list of scenes across ranks: each rank runs the pipeline on its LPT share, then (optionally)
     all ranks receive every frame.  ``scenes`` entries are dicts of the pipeline's tensor arguments for one
     scene (leading batch dimension 1); all scenes of one call have the same view count.  ``res`` is the pipeline's
-    ``resolution``: an int (square frames) or (height, width)."""
+    ``resolution``: an int (square frames) or (height, width).  Further keywords go to the pipeline unchanged
+    (``overscan=True``; a scene dict may hold ``intrinsics`` with ``fov`` None)."""
 
     def __init__(self, pipeline, rank: int = 0, world: int = 1):
         self.pipeline = pipeline
@@ -185,6 +186,8 @@ class ShardedRenderer:
         return out
 
     def _frame_shape(self, n_views: int, res):
+        """(V, H, W, C) of a scene's returned frames: the REQUESTED H x W, also under ``overscan=True`` (the pipeline
+        returns the requested window of the padded frame), so the gather slots need no flag."""
         h, w = frame_hw(res)
         return (n_views, h, w, frame_channels(self.pipeline.config))
 
@@ -216,7 +219,13 @@ class ShardedRenderer:
         if len(vr):
             sub = dict(scene)
             sub["c2w"] = scene["c2w"][:, vr.start:vr.stop].contiguous()
-            sub["fov"] = scene["fov"][:, vr.start:vr.stop].contiguous()
+            # the per-view camera arguments: fov, or intrinsics [1, V, 4] (in the scene dict or a keyword) with fov None
+            if scene.get("fov") is not None:
+                sub["fov"] = scene["fov"][:, vr.start:vr.stop].contiguous()
+            intr = kw.pop("intrinsics", scene.get("intrinsics"))
+            if intr is not None:
+                sub["intrinsics"] = intr[:, vr.start:vr.stop].contiguous()
+                sub.setdefault("fov", None)
             local = self._render_resolved(sub, res, kw)[0]
         else:
             local = torch.empty((0,) + shape, dtype=torch.float32, device=self.pipeline.device)
