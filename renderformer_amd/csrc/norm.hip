@@ -401,6 +401,17 @@ __global__ __launch_bounds__(256) void qk_norm_rope_row_kernel(const bf16_t* src
 }
 
 // ----------------------------------------------------------------------------- embedding assembly
+// The arithmetic both embedding kernels share, written out so that it does not depend on what the compiler fuses or
+// packs in either of them: a row that takes the scalar kernel only because a pointer or a stride is not 16-B aligned
+// gets the bits the vector kernel gives.  Lane l owns columns 4 l .. 4 l + 3 of every 256-column group; its four
+// squares are rounded one by one and added left to right (no contraction), the groups in ascending order; a
+// normalised term enters the sum as fma(x / rms, weight, sum so far).
+RF_DEV float embed_sumsq4(float x, float y, float z, float w) {
+#pragma clang fp contract(off)
+    return x * x + y * y + z * z + w * w;
+}
+RF_DEV float embed_add(float v, float x, float inv_rms, float g) { return __builtin_fmaf(x * inv_rms, g, v); }
+
 __global__ __launch_bounds__(256) void embed_kernel(float* __restrict__ out, int64_t ldo,
                                                     const int32_t* __restrict__ out_rows, int rows, int dim,
                                                     const float* __restrict__ base, int base_rows,
@@ -414,23 +425,22 @@ __global__ __launch_bounds__(256) void embed_kernel(float* __restrict__ out, int
     float s0 = 0.f, s1 = 0.f;
     const float* r0 = in0 ? in0 + (int64_t)row * ld0 : nullptr;
     const float* r1 = in1 ? in1 + (int64_t)row * ld1 : nullptr;
-    if (r0) {
+    auto sumsq = [&](const float* r) {  // (columns past dim count as 0: adding +0 changes nothing)
         float ss = 0.f;
-        for (int c = lane; c < dim; c += 64) ss += r0[c] * r0[c];
-        s0 = 1.0f / sqrtf(wave_sum(ss) / (float)dim + eps0);
-    }
-    if (r1) {
-        float ss = 0.f;
-        for (int c = lane; c < dim; c += 64) ss += r1[c] * r1[c];
-        s1 = 1.0f / sqrtf(wave_sum(ss) / (float)dim + eps1);
-    }
+        for (int c = 4 * lane; c < dim; c += 256)
+            ss += embed_sumsq4(r[c], c + 1 < dim ? r[c + 1] : 0.f, c + 2 < dim ? r[c + 2] : 0.f,
+                               c + 3 < dim ? r[c + 3] : 0.f);
+        return wave_sum(ss);
+    };
+    if (r0) s0 = 1.0f / sqrtf(sumsq(r0) / (float)dim + eps0);
+    if (r1) s1 = 1.0f / sqrtf(sumsq(r1) / (float)dim + eps1);
     const float* b = base ? base + (int64_t)(row % base_rows) * dim : nullptr;
     float* o = out + (int64_t)(out_rows ? out_rows[row] : row) * ldo;
     for (int c = lane; c < dim; c += 64) {
         // same association as the reference: (token + tex_emb) + vn_emb (renderformer.py:158)
         float v = b ? b[c] : 0.f;
-        if (r0) v = v + r0[c] * s0 * w0[c];
-        if (r1) v = v + r1[c] * s1 * w1[c];
+        if (r0) v = embed_add(v, r0[c], s0, w0[c]);
+        if (r1) v = embed_add(v, r1[c], s1, w1[c]);
         o[c] = v;
     }
 }
@@ -460,8 +470,8 @@ __global__ __launch_bounds__(256) void embed_v_kernel(float* __restrict__ out, i
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        s0 += a[i].x * a[i].x + a[i].y * a[i].y + a[i].z * a[i].z + a[i].w * a[i].w;
-        s1 += b[i].x * b[i].x + b[i].y * b[i].y + b[i].z * b[i].z + b[i].w * b[i].w;
+        s0 += embed_sumsq4(a[i].x, a[i].y, a[i].z, a[i].w);
+        s1 += embed_sumsq4(b[i].x, b[i].y, b[i].z, b[i].w);
     }
     s0 = in0 ? 1.0f / sqrtf(wave_sum(s0) / (float)(256 * NV) + eps0) : 0.f;
     s1 = in1 ? 1.0f / sqrtf(wave_sum(s1) / (float)(256 * NV) + eps1) : 0.f;
@@ -472,17 +482,17 @@ __global__ __launch_bounds__(256) void embed_v_kernel(float* __restrict__ out, i
         float4 v = t[i];
         if (in0) {
             const float4 g = reinterpret_cast<const float4*>(w0)[lane + 64 * i];
-            v.x = v.x + a[i].x * s0 * g.x;
-            v.y = v.y + a[i].y * s0 * g.y;
-            v.z = v.z + a[i].z * s0 * g.z;
-            v.w = v.w + a[i].w * s0 * g.w;
+            v.x = embed_add(v.x, a[i].x, s0, g.x);
+            v.y = embed_add(v.y, a[i].y, s0, g.y);
+            v.z = embed_add(v.z, a[i].z, s0, g.z);
+            v.w = embed_add(v.w, a[i].w, s0, g.w);
         }
         if (in1) {
             const float4 g = reinterpret_cast<const float4*>(w1)[lane + 64 * i];
-            v.x = v.x + b[i].x * s1 * g.x;
-            v.y = v.y + b[i].y * s1 * g.y;
-            v.z = v.z + b[i].z * s1 * g.z;
-            v.w = v.w + b[i].w * s1 * g.w;
+            v.x = embed_add(v.x, b[i].x, s1, g.x);
+            v.y = embed_add(v.y, b[i].y, s1, g.y);
+            v.z = embed_add(v.z, b[i].z, s1, g.z);
+            v.w = embed_add(v.w, b[i].w, s1, g.w);
         }
         o[lane + 64 * i] = v;
     }
