@@ -79,7 +79,8 @@ extern "C" {
 /* Still 16 with rf_scene_kv and rf_decoder_desc.kv_all / ld_kv_all: a new symbol and two trailing descriptor fields
  * that a zero-initialised caller leaves NULL / 0 (= the behaviour before them); nothing that existed changed.
  * Still 16 with rf_ray_tokens_hw / rf_patchify_rays_hw: two new symbols.
- * Still 16 with rf_ray_tokens_cam / rf_hdr_output_win / rf_frame_window: three new symbols. */
+ * Still 16 with rf_ray_tokens_cam / rf_hdr_output_win / rf_frame_window: three new symbols.
+ * Still 16 with rf_conv_plan_query: a new symbol. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -522,6 +523,34 @@ int rf_conv1x1_f16_group(int n_conv, const void* const* in, const int* cin_pad, 
 int rf_deconv2d_f16(const void* in, int n_img, int hi, int wi, int cin_pad, const void* w, int cout, int k,
                     const float* bias, float* out, void* p_out, int p_ld, void* workspace, int64_t ws_bytes,
                     void* stream);
+
+/* Diagnostics / tests: the kernel the four entry points above would launch for a call, under the RF_CONV_* knobs of
+ * the environment as it stands, without launching it (host arithmetic only: no device is needed).  operand:
+ * RF_DT_F16 (rf_conv2d_f16 / rf_deconv2d_f16) or RF_DT_BF16 (the bf16x3 pair); deconv_k > 0: the deconvolution with
+ * kernel == stride == deconv_k (cout_pad, kh, kw, stride, pad, flags, n_fin unused); ws_bytes: the stream-K
+ * workspace the call would pass (0: none).  RF_ERR_INVALID for the shapes the entry points reject.
+ * kernel: the family.  code: the variant within it -- the ring engine's tile as an RF_CONV_TILE code (64, 128, 256,
+ * 1288, 2561, 6412; 25664 = 256x64), HS the block geometry as an RF_CONV_HALO_SMALL code, HALO2 1000 x W ring depth
+ * + channels per block (4128, 3064, ...), PHASED 1 for the persistent form.  refuse: the call returns
+ * RF_ERR_UNSUPPORTED instead (a study-only kernel asked of the production build). */
+#define RF_CONVK_NONE 0      /* nothing to launch (no output pixels) */
+#define RF_CONVK_RING 1      /* ring engine, data-parallel */
+#define RF_CONVK_RING_SK 2   /* ring engine, stream-K */
+#define RF_CONVK_RING_HALO 3 /* ring engine's tile, halo-tiled (halo_kernel) */
+#define RF_CONVK_PHASED 4    /* phased 256x256 */
+#define RF_CONVK_HALO2 5
+#define RF_CONVK_HALO3 6
+#define RF_CONVK_C32 7
+#define RF_CONVK_HK 8
+#define RF_CONVK_HS 9
+typedef struct {
+    int kernel, code, grid, block; /* RF_CONVK_*, its variant, workgroups, threads per workgroup */
+    int halo_lg;                   /* RF_CONVK_RING_HALO: log2 of the tile width in pixels */
+    int dbg;                       /* study build: the RF_H2_DBG / RF_H3_DBG ablation variant */
+    int refuse;
+} rf_conv_plan;
+int rf_conv_plan_query(int operand, int deconv_k, int n_img, int hi, int wi, int cin_pad, int cout, int cout_pad, int kh,
+                       int kw, int stride, int pad, int flags, int n_fin, int64_t ws_bytes, rf_conv_plan* out);
 
 /* f32 rows x[r, 0:c] (row stride ldx) -> bf16 hi/lo planes (row stride p_ld), of silu(x) if silu_act.
  * p_lo == NULL: one fp16 plane in p_hi instead (input of rf_conv2d_f16 / rf_deconv2d_f16). */

@@ -87,6 +87,7 @@ SIGNATURES = {
     "rf_conv2d_f16": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _F,
                       _P, _L, _P],
     "rf_deconv2d_f16": [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _L, _P],
+    "rf_conv_plan_query": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P],
     "rf_split_planes": [_P, _L, _I, _L, _P, _P, _I, _I, _P],
     "rf_upsample_bilinear": [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P],
     "rf_upsample_bilinear_h": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
@@ -155,6 +156,20 @@ class DecoderDesc(ctypes.Structure):
                 ("attn_ws", _P), ("timer_cross", _I), ("qk_fused", _I), ("kv_all", _P), ("ld_kv_all", _L)]
 
 
+class ConvPlan(ctypes.Structure):
+    """rf.h rf_conv_plan: the kernel a convolution call launches (rf_conv_plan_query)"""
+    _fields_ = [(n, _I) for n in ("kernel", "code", "grid", "block", "halo_lg", "dbg", "refuse")]
+
+    def __repr__(self):
+        name = {v: k for k, v in CONVK.items()}.get(self.kernel, self.kernel)
+        return "ConvPlan(" + ", ".join([str(name)] + [f"{n}={getattr(self, n)}" for n, _ in self._fields_[1:]]) + ")"
+
+
+# rf.h RF_CONVK_*: the kernel families of a ConvPlan
+CONVK = {"none": 0, "ring": 1, "ring_sk": 2, "ring_halo": 3, "phased": 4, "halo2": 5, "halo3": 6, "c32": 7, "hk": 8,
+         "hs": 9}
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -211,6 +226,20 @@ def study_build() -> bool:
     if getattr(lib, "rf_build_flags", None) is None:  # a pre-round-5 library (RF_LIB): no study variants
         return False
     return bool(lib.rf_build_flags() & 1)
+
+
+def conv_plan(f16: bool, n_img: int, hi: int, wi: int, cin_pad: int, cout: int, cout_pad: int = 0, kh: int = 3,
+              kw: int = 3, stride: int = 1, pad: int = 1, flags: int = 0, n_fin: int = 0, deconv_k: int = 0,
+              ws_bytes: int = 0) -> ConvPlan:
+    """The kernel rf_conv2d_* / rf_deconv2d_* (deconv_k > 0) would launch for this call under the current RF_CONV_*
+    environment (rf_conv_plan_query: host arithmetic, no device needed).  ValueError for a shape they reject."""
+    lib = load(require_device=False)
+    out = ConvPlan()
+    rc = lib.rf_conv_plan_query(1 if f16 else 0, deconv_k, n_img, hi, wi, cin_pad, cout, cout_pad, kh, kw, stride, pad,
+                                flags, n_fin, ws_bytes, ctypes.addressof(out))
+    if rc != 0:
+        raise ValueError(lib.rf_last_error().decode(errors="replace"))
+    return out
 
 
 def call(name: str, *args) -> None:

@@ -3237,40 +3237,14 @@ int launch(EngineArgs a, void* stream, const char* what) {
     return rf::check_launch(what);
 }
 
-// the halo kernel serves this convolution: 3x3, stride 1, pad 1, whole tiles of TW | wo (power of 2) x TH
-template <class C>
-bool halo_ok(EngineArgs& a) {
-    if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
-    if (a.cin_pad % BK || a.m % C::BM || (a.ho * a.wo) % C::BM) return false;
-    const int tw = std::min(C::BM, a.wo);
-    if (tw < 16 || (tw & (tw - 1)) || a.wo % tw || C::BM % tw) return false;
-    const int th = C::BM / tw;
-    if (a.ho % th || (th + 2) * (tw + 2) > Halo<C>::ROWS) return false;
-    a.halo_lg = __builtin_ctz(tw);
-    return true;
-}
-
+// halo_kernel on tile C (conv_plan found the shape whole tiles of 2^halo_lg pixels wide: halo_tile_lg)
 template <class C, int EPI>
-int launch_halo(EngineArgs a, void* stream, const char* what) {
+int launch_halo(EngineArgs a, int halo_lg, void* stream, const char* what) {
     const int tiles_m = a.m / C::BM, tiles_n = a.n / C::BN;
-    const int nwg = tiles_n * tiles_m;
-    a.group_m = pick_group_m(tiles_m, tiles_n, C::BM, C::BN, (nwg + 7) / 8);
-    RF_LAUNCH((halo_kernel<C, EPI>), dim3(nwg), dim3(C::THREADS), 0, (hipStream_t)stream, a);
+    a.halo_lg = halo_lg;
+    a.group_m = pick_group_m(tiles_m, tiles_n, C::BM, C::BN, (tiles_n * tiles_m + 7) / 8);
+    RF_LAUNCH((halo_kernel<C, EPI>), dim3(tiles_n * tiles_m), dim3(C::THREADS), 0, (hipStream_t)stream, a);
     return rf::check_launch(what);
-}
-
-// the engine's data-parallel conv launch, or the halo kernel when it serves the shape
-// Measured (tools/kbench.py conv, RF_CONV_HALO): the halo kernel wins on the 4-wave 128x128 tile at large
-// grids (512^2 output_conv1, 256 -> 128: 293 -> 251 us), where the gathered A re-reads dominate; on the
-// 8-wave tiles it loses (128^2: 45 -> 49 us; 256^2 256x256: 123 -> 258 us, the tile spills), so by
-// default only T128 uses it (RF_CONV_HALO=1: every tile that can, 0: none).
-template <class C, int NTERM, bool GATHER>
-int launch_conv(EngineArgs& a, void* stream, const char* what) {
-    if constexpr (GATHER && NTERM == P_F16) {
-        const bool want = rf::env_int("RF_CONV_HALO", C::BM == 128 && C::NWAVE == 4) != 0;
-        if (want && halo_ok<C>(a)) return launch_halo<C, E_CONV>(a, stream, what);
-    }
-    return launch<C, E_CONV, NTERM, GATHER>(a, stream, what);
 }
 
 constexpr int SK_MAX_GRID = 768;                                  // 3 blocks of T128 per CU
@@ -3775,13 +3749,16 @@ bool persist_ragged() {
     return RF_ENV_ONCE("RF_GEMM_PERSIST_RAGGED", 0) != 0;
 }
 
+// launch_phased's persistent form serves this many 256x256 tiles of dense operands (conv_plan asks too)
+bool phased_persists(int nwg) { return nwg > 256 && persist_on() && (nwg % 256 == 0 || persist_ragged()); }
+
 template <int EPI, int NTERM, bool GATHER, int BM = 256>
 int launch_phased(EngineArgs a, void* stream, const char* what) {
     const int tiles_m = (a.m + BM - 1) / BM, tiles_n = a.n / 256;
     const int nwg = tiles_n * tiles_m;
     a.group_m = pick_group_m(tiles_m, tiles_n, BM, 256, (nwg + 7) / 8, GATHER ? 0 : (int64_t)a.m * a.k * 2);
     if constexpr (BM == 256 && (NTERM == 1 || NTERM == P_F16) && !GATHER) {
-        if (nwg > 256 && persist_on() && (nwg % 256 == 0 || persist_ragged())) {
+        if (phased_persists(nwg)) {
             a.persist = 1;
             RF_LAUNCH((phased_sk_kernel<EPI, NTERM>), dim3(256), dim3(512), 0, (hipStream_t)stream, a);
             return rf::check_launch(what);
@@ -4247,176 +4224,11 @@ extern "C" int rf_quant_mx8(const void* x, int64_t ldx, int rows, int cols, void
     return rf::check_launch("rf_quant_mx8");
 }
 
-// halo2_kernel serves 3x3 / stride 1 / pad 1 fp16 convolutions on whole 16 x 32 tiles with a multiple of 128
-// output channels (or 64: output_conv2) when they make at least one block per CU (RF_CONV_HALO2=0: never,
-// 1: whenever it can)
-static bool halo2_ok(const EngineArgs& a) {
-    const int env = rf::env_int("RF_CONV_HALO2", -1);  // (-1: unset)
-    if (env == 0) return false;
-    if (!rf::env_set("RF_CONV_HALO2") && rf::env_set("RF_CONV_TILE")) return false;  // an explicit tile choice (A/B, tests) keeps its kernel
-    if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
-    if (a.cin_pad % 32 || (a.n % 128 && a.n != 64) || a.ho % h2::TH || a.wo % h2::TW || a.m % 512) return false;
-    const int64_t blocks = (int64_t)(a.m / 512) * (a.n == 64 ? 1 : a.n / 128);
-    return env == 1 || blocks >= 256;
-}
-
-static int launch_halo2(EngineArgs a, void* stream, const char* what) {
-    const bool n64 = a.n == 64;
-    const int nwg = (a.m / 512) * (n64 ? 1 : a.n / 128);
-    const int ring = rf::env_int("RF_CONV_H2S", 4);  // W ring depth (slices in flight + 1): 4 (default), 3 or 5
-    const hipStream_t st = (hipStream_t)stream;
-    const int dbg = rf::env_int("RF_H2_DBG", 0);  // ablation timing only
-#ifndef RF_STUDY
-    if (dbg) return rf::study_only("rf_conv: RF_H2_DBG (halo2 ablation builds)");
-#else
-    if (!n64 && ring == 4 && dbg >= 1 && dbg <= 8) {
-        if (dbg == 1) RF_LAUNCH((halo2_kernel<4, 128, 1>), dim3(nwg), dim3(512), 0, st, a);
-        if (dbg == 2) RF_LAUNCH((halo2_kernel<4, 128, 2>), dim3(nwg), dim3(512), 0, st, a);
-        if (dbg == 3) RF_LAUNCH((halo2_kernel<4, 128, 3>), dim3(nwg), dim3(512), 0, st, a);
-        if (dbg == 4) RF_LAUNCH((halo2_kernel<4, 128, 4>), dim3(nwg), dim3(512), 0, st, a);
-        if (dbg == 8) RF_LAUNCH((halo2_kernel<4, 128, 8>), dim3(nwg), dim3(512), 0, st, a);
-        return rf::check_launch(what);
-    }
-#endif
-    if (n64) {
-        if (ring == 3) RF_LAUNCH((halo2_kernel<3, 64>), dim3(nwg), dim3(512), 0, st, a);
-        else if (ring == 5) RF_LAUNCH((halo2_kernel<5, 64>), dim3(nwg), dim3(512), 0, st, a);
-        else RF_LAUNCH((halo2_kernel<4, 64>), dim3(nwg), dim3(512), 0, st, a);
-    } else {
-        if (ring == 3) RF_LAUNCH((halo2_kernel<3, 128>), dim3(nwg), dim3(512), 0, st, a);
-        else if (ring == 5) RF_LAUNCH((halo2_kernel<5, 128>), dim3(nwg), dim3(512), 0, st, a);
-        else RF_LAUNCH((halo2_kernel<4, 128>), dim3(nwg), dim3(512), 0, st, a);
-    }
-    return rf::check_launch(what);
-}
-
-// halo3_kernel serves halo2's non-final convolutions with a multiple of 128 output channels (RF_CONV_HALO3=0:
-// halo2 instead); the bank must be addressable by 32-bit buffer offsets
-static bool halo3_ok(const EngineArgs& a) {
-    if (rf::env_int("RF_CONV_HALO3", 1) == 0 || (a.flags & RF_CONV_FINAL) || a.n % 128 || a.deconv) return false;
-    if ((int64_t)128 * a.ldw * 2 >= 0x7fffffff) return false;
-    return halo2_ok(a);
-}
-
-static int launch_halo3(EngineArgs a, void* stream, const char* what) {
-    const int nwg = (a.m / 512) * (a.n / 128);
-    const int dbg = rf::env_int("RF_H3_DBG", 0);  // ablation timing only
-#ifndef RF_STUDY
-    if (dbg) return rf::study_only("rf_conv: RF_H3_DBG (halo3 ablation builds, garbage results)");
-    RF_LAUNCH(halo3_kernel<0>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-#else
-    if (dbg == 1) RF_LAUNCH(halo3_kernel<1>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 2) RF_LAUNCH(halo3_kernel<2>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 4) RF_LAUNCH(halo3_kernel<4>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 6) RF_LAUNCH(halo3_kernel<6>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 8) RF_LAUNCH(halo3_kernel<8>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 14) RF_LAUNCH(halo3_kernel<14>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 15) RF_LAUNCH(halo3_kernel<15>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 30) RF_LAUNCH(halo3_kernel<30>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 16) RF_LAUNCH(halo3_kernel<16>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 32) RF_LAUNCH(halo3_kernel<32>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 64) RF_LAUNCH(halo3_kernel<64>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else if (dbg == 96) RF_LAUNCH(halo3_kernel<96>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-    else RF_LAUNCH(halo3_kernel<0>, dim3(nwg), dim3(512), 0, (hipStream_t)stream, a);
-#endif
-    return rf::check_launch(what);
-}
-
-// conv3x3_c32_kernel serves the fused-head 3x3 convolution with <= 32 filters (output_conv2) on whole 16 x 32
-// tiles (RF_CONV_C32=0: the halo2 / engine paths instead)
-static bool c32_ok(const EngineArgs& a) {
-    if (rf::env_int("RF_CONV_C32", 1) == 0 || !(a.flags & RF_CONV_FINAL) || a.cout > 32 || a.n < 32) return false;
-    if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
-    return a.cin_pad % 32 == 0 && a.ho % c32::TH == 0 && a.wo % c32::TW == 0 && a.m > 0 && a.n_fin <= c32::NFIN;
-}
-
-static int launch_c32(EngineArgs a, void* stream, const char* what) {
-    const int nwg = a.m / (c32::TH * c32::TW);
-    RF_LAUNCH(conv3x3_c32_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, a);
-    return rf::check_launch(what);
-}
-
-// conv3x3_hk_kernel serves non-final 3x3 / stride 1 / pad 1 fp16 convolutions on whole 16 x 32 tiles with a
-// multiple of 64 output channels and at least one block per CU (RF_CONV_HK=0: the halo2 / engine paths; 1: whenever
-// it can)
-static bool hk_ok(const EngineArgs& a) {
-    const int env = rf::env_int("RF_CONV_HK", 0);
-    if (env == 0 || (a.flags & RF_CONV_FINAL) || a.deconv) return false;  // opt-in: see DESIGN §3.4
-#ifndef RF_STUDY
-    return true;  // (the production build refuses it in launch_hk)
-#else
-    if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return false;
-    if (a.cin_pad % 32 || a.n % hk::NCO || a.ho % hk::TH || a.wo % hk::TW || a.m <= 0) return false;
-    return env == 1 || (int64_t)(a.m / (hk::TH * hk::TW)) * (a.n / hk::NCO) >= 256;
-#endif
-}
-
-static int launch_hk(EngineArgs a, void* stream, const char* what) {
-#ifdef RF_STUDY
-    const int nwg = (a.m / (hk::TH * hk::TW)) * (a.n / hk::NCO);
-    RF_LAUNCH(conv3x3_hk_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, a);
-    return rf::check_launch(what);
-#else
-    (void)a, (void)stream, (void)what;
-    return rf::study_only("rf_conv: RF_CONV_HK=1 (conv3x3_hk_kernel)");
-#endif
-}
-
-// conv3x3_hs_kernel serves the non-final 3x3 / stride 1 / pad 1 fp16 convolutions with a multiple of 32 filters
-// whose image is too small for halo2 / halo3's blocks to fill the chip (RF_CONV_HALO_SMALL=0: the gathered engine
-// launches instead; 1, the default: the largest block geometry that still makes >= 256 blocks, else the smallest;
-// a geometry code below: that geometry wherever the image admits it).  An explicit RF_CONV_TILE keeps its kernel.
-enum HsGeom : int { HS_NONE = 0, HS_16x32x64 = 163264, HS_16x32x32 = 163232, HS_8x16x64 = 81664, HS_8x16x32 = 81632 };
-struct HsChoice {
-    int code, th, tw, bn;
-};
-static constexpr HsChoice HS_GEOMS[] = {  // largest block first
-    {HS_16x32x64, 16, 32, 64}, {HS_16x32x32, 16, 32, 32}, {HS_8x16x64, 8, 16, 64}, {HS_8x16x32, 8, 16, 32}};
-static int64_t hs_blocks(const EngineArgs& a, const HsChoice& g) {  // 0: the geometry does not admit the launch
-    if (a.ho % g.th || a.wo % g.tw || a.cout % g.bn) return 0;
-    return (int64_t)(a.m / (g.th * g.tw)) * (a.cout / g.bn);
-}
-static int hs_pick(const EngineArgs& a) {
-    const int env = rf::env_int("RF_CONV_HALO_SMALL", 1);
-    if (env == 0 || (a.flags & RF_CONV_FINAL) || a.deconv || a.m <= 0) return HS_NONE;
-    if (!rf::env_set("RF_CONV_HALO_SMALL") && rf::env_set("RF_CONV_TILE")) return HS_NONE;
-    if (a.kw != 3 || a.k != 9 * a.cin_pad || a.stride != 1 || a.pad != 1 || a.ho != a.hi || a.wo != a.wi) return HS_NONE;
-    if (a.cin_pad % 32 || a.cout % 32 || a.cout > a.n) return HS_NONE;
-    // halo2 / halo3's shapes stay theirs, whichever knob decides between them and the engine
-    if (a.ho % h2::TH == 0 && a.wo % h2::TW == 0 && (a.n % 128 == 0 || a.n == 64) &&
-        (int64_t)(a.m / 512) * (a.n == 64 ? 1 : a.n / 128) >= 256)
-        return HS_NONE;
-    if (env != 1) {
-        for (const HsChoice& g : HS_GEOMS)
-            if (g.code == env) return hs_blocks(a, g) ? g.code : HS_NONE;
-        return HS_NONE;
-    }
-    int code = HS_NONE;
-    for (const HsChoice& g : HS_GEOMS) {
-        const int64_t blocks = hs_blocks(a, g);
-        if (blocks) code = g.code;
-        if (blocks >= 256) break;
-    }
-    return code;
-}
-
-template <int TH, int TW, int BN>
-static int launch_hs_t(const EngineArgs& a, void* stream, const char* what) {
-    const int tiles_n = a.cout / BN;
-    const int nwg = (a.m / (TH * TW)) * tiles_n;
-    RF_LAUNCH((conv3x3_hs_kernel<TH, TW, BN>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, a, tiles_n);
-    return rf::check_launch(what);
-}
-
-static int launch_hs(const EngineArgs& a, int code, void* stream, const char* what) {
-    if (code == HS_16x32x64) return launch_hs_t<16, 32, 64>(a, stream, what);
-    if (code == HS_16x32x32) return launch_hs_t<16, 32, 32>(a, stream, what);
-    if (code == HS_8x16x64) return launch_hs_t<8, 16, 64>(a, stream, what);
-    return launch_hs_t<8, 16, 32>(a, stream, what);
-}
-
-// Conv tile codes: what RF_CONV_TILE=<number> forces (tests and tools/kbench.py pass these numbers); unset = CT_AUTO,
-// the heuristics of conv_common / conv_f16_dp.  Unrelated to the dense GEMM's RF_GEMM_TILE codes.
+// Convolution dispatch: conv_plan chooses the kernel of a convolution or deconvolution (host arithmetic on the
+// EngineArgs and the RF_CONV_* knobs, no HIP call), conv_run is the one switch from a plan to its launch, and
+// rf_conv_plan_query (rf.h) returns the plan of a call without running it.
+// Conv tile codes: what RF_CONV_TILE=<number> forces (tests and tools/kbench.py pass these numbers) and what a ring
+// engine plan carries; unset = CT_AUTO, the heuristics of conv_plan.  Unrelated to the dense GEMM's RF_GEMM_TILE codes.
 enum ConvTile : int {
     CT_AUTO = 0,
     CT_64 = 64,          // 64x64 (T64c), data-parallel
@@ -4425,86 +4237,390 @@ enum ConvTile : int {
     CT_128w8 = 1288,     // fp16: 128x128, 8 waves
     CT_256x128 = 2561,   // fp16: 256x128, 8 waves
     CT_64x128 = 6412,    // fp16: 64x128 (T64x128c)
-    CT_64SK = 6464,      // fp16: 64x64, stream-K when the grid allows (conv_common), else data-parallel
+    CT_64SK = 6464,      // fp16: 64x64, stream-K when the grid allows, else data-parallel
+    CT_256x64 = 25664,   // plans only (RF_CONV_TILE does not force it): fp16 256x64, banks of 64 filters
 };
-static int conv_tile_env() { return rf::env_int("RF_CONV_TILE", CT_AUTO); }
 
-// fp16 convolutions (one MFMA per product): the 256x256 tile when the filter bank is a multiple of 256
-// wide and there is >= one tile per CU (the im2col gather of A is then read once per pixel tile),
-// 256x64 for <= 64 output channels, else 128x128 (faster than 256x128 on every DPT shape measured)
-template <bool GATHER>
-static int conv_f16_dp(EngineArgs& p, void* stream, const char* what, int tile = 0) {
-    if (GATHER && c32_ok(p)) return launch_c32(p, stream, what);
-    if (GATHER && hk_ok(p)) return launch_hk(p, stream, what);
-    if (GATHER && halo3_ok(p)) return launch_halo3(p, stream, what);
-    if (GATHER && halo2_ok(p)) return launch_halo2(p, stream, what);
-    const int t = tile ? tile : conv_tile_env();
+// conv3x3_hs_kernel's block geometries (RF_CONV_HALO_SMALL=<code> forces one), largest block first
+enum HsGeom : int { HS_NONE = 0, HS_16x32x64 = 163264, HS_16x32x32 = 163232, HS_8x16x64 = 81664, HS_8x16x32 = 81632 };
+struct HsChoice {
+    int code, th, tw, bn;
+};
+static constexpr HsChoice HS_GEOMS[] = {
+    {HS_16x32x64, 16, 32, 64}, {HS_16x32x32, 16, 32, 32}, {HS_8x16x64, 8, 16, 64}, {HS_8x16x32, 8, 16, 32}};
+
+struct ConvPlan {
+    int kernel = RF_CONVK_NONE;  // RF_CONVK_*, and in `code` the variant within it (rf.h, rf_conv_plan)
+    int code = 0, grid = 0, block = 0;
+    int halo_lg = 0;               // RING_HALO: log2 of the tile width in pixels
+    int dbg = 0;                   // study build: the RF_H2_DBG / RF_H3_DBG ablation instantiation
+    const char* refuse = nullptr;  // a study-only request in a production build: what rf::study_only reports
+};
+
+// 3x3, stride 1, pad 1: the output image has the input's size (every halo-tiled kernel's domain)
+static bool conv3x3_same(const EngineArgs& a) {
+    return a.kw == 3 && a.k == 9 * a.cin_pad && a.stride == 1 && a.pad == 1 && a.ho == a.hi && a.wo == a.wi;
+}
+
+// Blocks each halo-tiled kernel would launch for the conv3x3_same convolution a; 0: its tiling does not admit a
+static int64_t h2_blocks(const EngineArgs& a) {  // halo2 / halo3: 16 x 32 pixels x 128 filters (or the one bank of 64)
+    if (a.cin_pad % 32 || (a.n % 128 && a.n != 64) || a.ho % h2::TH || a.wo % h2::TW || a.m % 512) return 0;
+    return (int64_t)(a.m / 512) * (a.n == 64 ? 1 : a.n / 128);
+}
+static int64_t c32_blocks(const EngineArgs& a) {  // 16 x 32 pixels x every filter
+    if (a.cin_pad % 32 || a.ho % c32::TH || a.wo % c32::TW || a.m <= 0) return 0;
+    return a.m / (c32::TH * c32::TW);
+}
+#ifdef RF_STUDY
+static int64_t hk_blocks(const EngineArgs& a) {  // 16 x 32 pixels x 64 filters
+    if (a.cin_pad % 32 || a.n % hk::NCO || a.ho % hk::TH || a.wo % hk::TW || a.m <= 0) return 0;
+    return (int64_t)(a.m / (hk::TH * hk::TW)) * (a.n / hk::NCO);
+}
+#endif
+static int64_t hs_blocks(const EngineArgs& a, const HsChoice& g) {
+    if (a.ho % g.th || a.wo % g.tw || a.cout % g.bn) return 0;
+    return (int64_t)(a.m / (g.th * g.tw)) * (a.cout / g.bn);
+}
+// halo_kernel on a tile of bm pixels with `rows` LDS halo rows (Halo<C>::ROWS): whole tiles of TW | wo (a power
+// of 2) x TH; log2(TW), or 0 when it cannot
+static int halo_tile_lg(const EngineArgs& a, int bm, int rows) {
+    if (!conv3x3_same(a) || a.cin_pad % BK || a.m % bm || (a.ho * a.wo) % bm) return 0;
+    const int tw = std::min(bm, a.wo);
+    if (tw < 16 || (tw & (tw - 1)) || a.wo % tw || bm % tw) return 0;
+    const int th = bm / tw;
+    if (a.ho % th || (th + 2) * (tw + 2) > rows) return 0;
+    return __builtin_ctz(tw);
+}
+
+// The ring engine's launch on tile t: stream-K over sk_grid blocks, else data-parallel -- on halo_kernel when
+// `halo` (an fp16 convolution) allows and it serves the shape.
+// Measured (tools/kbench.py conv, RF_CONV_HALO): the halo kernel wins on the 4-wave 128x128 tile at large
+// grids (512^2 output_conv1, 256 -> 128: 293 -> 251 us), where the gathered A re-reads dominate; on the
+// 8-wave tiles it loses (128^2: 45 -> 49 us; 256^2 256x256: 123 -> 258 us, the tile spills), so by
+// default only T128 uses it (RF_CONV_HALO=1: every tile that can, 0: none).
+template <class C>
+static ConvPlan ring_plan(const EngineArgs& p, bool halo, ConvTile t, int64_t sk_grid = 0) {
+    ConvPlan pl{sk_grid ? RF_CONVK_RING_SK : RF_CONVK_RING, t,
+                sk_grid ? (int)sk_grid : ((p.m + C::BM - 1) / C::BM) * (p.n / C::BN), C::THREADS};
+    if (!sk_grid && halo && rf::env_int("RF_CONV_HALO", C::BM == 128 && C::NWAVE == 4) != 0 &&
+        (pl.halo_lg = halo_tile_lg(p, C::BM, Halo<C>::ROWS)) != 0)
+        pl.kernel = RF_CONVK_RING_HALO;
+    return pl;
+}
+
+// nterm: 3 = bf16x3 hi/lo operands, P_F16 = one fp16 plane per operand; gather: a convolution (false: a
+// deconvolution, dense A); ws_ok: the caller gave a stream-K workspace.  The rules are tried top to bottom.
+static ConvPlan conv_plan(const EngineArgs& p, int nterm, bool gather, bool ws_ok) {
+    if (p.m <= 0) return ConvPlan{};
+    const bool f16 = nterm == P_F16, fin = (p.flags & RF_CONV_FINAL) != 0;
+    const bool tile_set = rf::env_set("RF_CONV_TILE");
+    const int tile_env = rf::env_int("RF_CONV_TILE", CT_AUTO);
+    int ct = tile_env;  // the tile asked for: RF_CONV_TILE's, or rule 2's
+    // The halo-tiled kernels: fp16 3x3 convolutions.  Which of the 16 x 32-pixel ones would take this shape:
+    const bool same3 = f16 && gather && conv3x3_same(p);
+    // halo2_kernel: whole 16 x 32 tiles with a multiple of 128 output channels (or 64: output_conv2) when they make
+    // at least one block per CU (RF_CONV_HALO2=0: never, 1: whenever it can); an explicit tile choice (A/B, tests)
+    // keeps its kernel
+    const int h2_env = rf::env_int("RF_CONV_HALO2", -1);  // (-1: unset)
+    const int64_t h2b = same3 ? h2_blocks(p) : 0;
+    const bool h2 = h2_env != 0 && (rf::env_set("RF_CONV_HALO2") || !tile_set) && h2b && (h2_env == 1 || h2b >= 256);
+    // halo3_kernel: halo2's non-final convolutions with a multiple of 128 output channels (RF_CONV_HALO3=0: halo2
+    // instead); the bank must be addressable by 32-bit buffer offsets
+    const bool h3 = h2 && rf::env_int("RF_CONV_HALO3", 1) != 0 && !fin && p.n % 128 == 0 &&
+                    (int64_t)128 * p.ldw * 2 < 0x7fffffff;
+    // conv3x3_hk_kernel: non-final, a multiple of 64 output channels and at least one block per CU (RF_CONV_HK=0,
+    // the default: off; 1: whenever it can).  A production build takes every request and refuses
+    // it below
+    const int hk_env = f16 && gather && !fin ? rf::env_int("RF_CONV_HK", 0) : 0;
+#ifdef RF_STUDY
+    const int64_t hkb = hk_env && same3 ? hk_blocks(p) : 0;
+    const bool hk = hkb && (hk_env == 1 || hkb >= 256);
+#else
+    const bool hk = hk_env != 0;
+#endif
+    // 1. conv3x3_hs_kernel: non-final convolutions with a multiple of 32 filters whose image is too small for halo2 /
+    // halo3's blocks to fill the chip, ahead of the small-level tiles and the stream-K split below (all gathered
+    // engine launches).  RF_CONV_HALO_SMALL=0: those instead; 1, the default: the largest block geometry that still
+    // makes >= 256 blocks, else the smallest; a geometry code: that geometry wherever the image admits it.  An
+    // explicit RF_CONV_TILE keeps its kernel.  halo2 / halo3's shapes (>= 256 of their blocks) stay theirs, whichever
+    // knob decides between them and the engine
+    const int hs_env = same3 && !hk && !h3 && !h2 && !fin ? rf::env_int("RF_CONV_HALO_SMALL", 1) : 0;
+    if (hs_env != 0 && (rf::env_set("RF_CONV_HALO_SMALL") || !tile_set) && p.cin_pad % 32 == 0 && p.cout % 32 == 0 &&
+        p.cout <= p.n && h2b < 256) {
+        const HsChoice* pick = nullptr;
+        for (const HsChoice& g : HS_GEOMS) {
+            const int64_t blocks = hs_blocks(p, g);
+            if (blocks && (hs_env == 1 || hs_env == g.code)) pick = &g;
+            if (hs_env == 1 && blocks >= 256) break;
+        }
+        if (pick) return ConvPlan{RF_CONVK_HS, pick->code, (int)hs_blocks(p, *pick), 256};
+    }
+    // 2. small DPT levels (<= 4,096 output pixels per launch: the 64^2 / 32^2 refinenets and their rn convs): the
+    // 64x64 tile, data-parallel at K <= 2,304 and stream-K above (GPU time per launch, rocprofv3 over
+    // tools/kbench.py conv: 256->256 @32 32.4 -> 26.6 us, @64 30.1 -> 27.6 us, 1024->256 @32 50.4 -> 41.4 us;
+    // 1024->256 @64 stays on the default, 54.4 vs 68.1 us).  RF_CONV_SMALL=0 keeps the default tiles.
+    if (!ct && RF_ENV_ONCE("RF_CONV_SMALL", 1) != 0 && f16 && gather && p.kw == 3 && p.n % 64 == 0 && p.m <= 4096 &&
+        (p.k <= 2304 || p.m <= 1024))
+        ct = p.k <= 2304 ? CT_64 : CT_64SK;
+    // 3. stream-K over the 64x64 small-level tile, up to two blocks per CU, >= 12 K-steps per block
+    if (f16 && ct == CT_64SK && p.n % 64 == 0 && ws_ok) {
+        const int64_t tiles = (int64_t)((p.m + 63) / 64) * (p.n / 64);
+        const int64_t grid = std::min<int64_t>(512, tiles * (p.k / BK) / 12);
+        if (grid > tiles) return ring_plan<T64c>(p, false, CT_64, grid);
+    }
+    // 4. too few 128x128 tiles for 256 CUs (one bf16x3 block per CU): stream-K over the K loop, each block keeping
+    // >= 8 K-steps (RF_CONV_SK=0: never).  fp16 convolutions stream-K over the 8-wave tile (64^2 / 32^2 DPT levels:
+    // 1.6x / 2.1x; RF_CONV_SKW8=0: the 4-wave one).  `big`: 256x128 (8 waves) halves the L2 traffic per FLOP of the
+    // 128x128 tile but runs one block per CU: used only when it still yields >= one tile per CU.
+    const bool big = tile_set ? ct == CT_256 : ((p.m + 255) / 256) * (p.n / 128) >= 256;
+    if (!big && p.n % 128 == 0 && ws_ok && rf::env_int("RF_CONV_SK", 1) != 0 &&
+        !(f16 && (ct == CT_64 || ct == CT_64x128 || ct == CT_64SK))) {
+        const int64_t tiles = (int64_t)((p.m + 127) / 128) * (p.n / 128);
+        const int64_t grid = std::min<int64_t>(256, tiles * (p.k / BK) / 8);
+        if (tiles < 192 && grid > tiles)
+            return f16 && rf::env_int("RF_CONV_SKW8", 1) != 0 ? ring_plan<T128w8>(p, false, CT_128w8, grid)
+                                                              : ring_plan<T128>(p, false, CT_128, grid);
+    }
+    // 5. bf16x3 operands: the data-parallel ring engine
+    if (!f16) return big ? ring_plan<T256x128>(p, false, CT_256x128) : ring_plan<T128>(p, false, CT_128);
+    // 6. the 16 x 32-pixel halo-tiled kernels.  conv3x3_c32_kernel: the fused-head convolution with <= 32 filters
+    // (output_conv2) on whole tiles
+    // (RF_CONV_C32=0: the halo2 / engine paths instead)
+    if (same3 && fin && rf::env_int("RF_CONV_C32", 1) != 0 && p.cout <= 32 && p.n >= 32 && p.n_fin <= c32::NFIN)
+        if (const int64_t blocks = c32_blocks(p)) return ConvPlan{RF_CONVK_C32, 0, (int)blocks, 256};
+    if (hk) {
+#ifdef RF_STUDY
+        return ConvPlan{RF_CONVK_HK, 0, (int)hkb, 256};
+#else
+        return ConvPlan{RF_CONVK_HK, 0, 0, 256, 0, 0, "rf_conv: RF_CONV_HK=1 (conv3x3_hk_kernel)"};
+#endif
+    }
+    if (h3) {
+        ConvPlan pl{RF_CONVK_HALO3, 0, (int)h2b, 512};
+        pl.dbg = rf::env_int("RF_H3_DBG", 0);  // ablation timing only
+#ifndef RF_STUDY
+        if (pl.dbg) pl.refuse = "rf_conv: RF_H3_DBG (halo3 ablation builds, garbage results)";
+#endif
+        return pl;
+    }
+    if (h2) {
+        const int ring = rf::env_int("RF_CONV_H2S", 4);  // W ring depth (slices in flight + 1): 4 (default), 3 or 5
+        ConvPlan pl{RF_CONVK_HALO2, 1000 * (ring == 3 || ring == 5 ? ring : 4) + (p.n == 64 ? 64 : 128), (int)h2b, 512};
+        const int dbg = rf::env_int("RF_H2_DBG", 0);  // ablation timing only
+#ifdef RF_STUDY
+        if (p.n != 64 && ring == 4 && dbg >= 1 && dbg <= 8) pl.dbg = dbg;
+#else
+        if (dbg) pl.refuse = "rf_conv: RF_H2_DBG (halo2 ablation builds)";
+#endif
+        return pl;
+    }
+    // 7. fp16 on the data-parallel ring engine (one MFMA per product): 256x64 for a bank of 64 output channels, the
+    // tile RF_CONV_TILE or rule 2 names, the 256x256 tile when the filter bank is a multiple of 256 wide and there
+    // is >= one tile per CU (the im2col gather of A is then read once per pixel tile), else 128x128 (faster than
+    // 256x128 on every DPT shape measured)
+    const int t = ct == CT_64 ? CT_64 : tile_env;
     // (RF_CONV_HALO=1 runs it halo-tiled: 90 -> 140 us at 512^2, 128 -> 32; a 128x64 tile at two blocks per
     // CU measured the same 90 us with or without the halo, so the gathered 256x64 launch stays the default)
-    if (p.n == 64) return launch_conv<T256x64, P_F16, GATHER>(p, stream, what);
-    if (t == CT_64 || t == CT_64SK) return launch_conv<T64c, P_F16, GATHER>(p, stream, what);
-    if (t == CT_64x128) return launch_conv<T64x128c, P_F16, GATHER>(p, stream, what);
-    if (t == CT_128) return launch_conv<T128, P_F16, GATHER>(p, stream, what);
-    if (t == CT_128w8) return launch_conv<T128w8, P_F16, GATHER>(p, stream, what);
-    if (t == CT_256x128) return launch<T256x128, E_CONV, P_F16, GATHER>(p, stream, what);  // (never the halo kernel)
-    if (p.n % 256 == 0 && (t == CT_256 || (t == CT_AUTO && ((p.m + 255) / 256) * (p.n / 256) >= 256)))
-        return (rf::env_int("RF_CONV_PHASED", 0) != 0 && use_phased(p.n, p.k))
-                   ? launch_phased<E_CONV, P_F16, GATHER, 256>(p, stream, what)
-                   : launch_conv<T256, P_F16, GATHER>(p, stream, what);
+    if (p.n == 64) return ring_plan<T256x64>(p, gather, CT_256x64);
+    if (t == CT_64 || t == CT_64SK) return ring_plan<T64c>(p, gather, CT_64);
+    if (t == CT_64x128) return ring_plan<T64x128c>(p, gather, CT_64x128);
+    if (t == CT_128) return ring_plan<T128>(p, gather, CT_128);
+    if (t == CT_128w8) return ring_plan<T128w8>(p, gather, CT_128w8);
+    if (t == CT_256x128) return ring_plan<T256x128>(p, false, CT_256x128);  // (never the halo kernel)
+    if (p.n % 256 == 0 && (t == CT_256 || (t == CT_AUTO && ((p.m + 255) / 256) * (p.n / 256) >= 256))) {
+        if (rf::env_int("RF_CONV_PHASED", 0) == 0 || !use_phased(p.n, p.k)) return ring_plan<T256>(p, gather, CT_256);
+        const int nwg = ((p.m + 255) / 256) * (p.n / 256);
+        const bool persist = !gather && phased_persists(nwg);  // (a deconvolution's dense A: launch_phased)
+        return ConvPlan{RF_CONVK_PHASED, persist, persist ? 256 : nwg, 512};
+    }
     // up to two 128x128 tiles per CU: the 8-wave tile (two waves per SIMD) hides the gathered staging's
     // latency (128^2 DPT level: 52 -> 41 us); with more tiles the 4-wave tile's extra blocks do that
     const int64_t tiles = (int64_t)((p.m + 127) / 128) * (p.n / 128);
-    if (tiles <= 512) return launch_conv<T128w8, P_F16, GATHER>(p, stream, what);
-    return launch_conv<T128, P_F16, GATHER>(p, stream, what);
+    return tiles <= 512 ? ring_plan<T128w8>(p, gather, CT_128w8) : ring_plan<T128>(p, gather, CT_128);
 }
 
-template <int NT>
-static int conv_dispatch(EngineArgs& p, bool gather, bool big, int64_t sk_grid_n, void* workspace, void* stream,
-                         const char* what, int tile = 0) {
-    if constexpr (NT == P_F16) {
-        if (!sk_grid_n)
-            return gather ? conv_f16_dp<true>(p, stream, what, tile) : conv_f16_dp<false>(p, stream, what, tile);
+// fp16 data-parallel on tile C, halo-tiled when the plan says so
+template <class C, bool GATHER>
+static int run_ring_f16(const ConvPlan& pl, const EngineArgs& a, void* stream, const char* what) {
+    if constexpr (GATHER) {
+        if (pl.kernel == RF_CONVK_RING_HALO) return launch_halo<C, E_CONV>(a, pl.halo_lg, stream, what);
     }
-    if (sk_grid_n) {
-        if (const int rc = sk_setup(p, workspace, stream)) return rc;
-        // fp16 convolutions stream-K over the 8-wave 128x128 tile (64^2 / 32^2 DPT levels: 1.6x / 2.1x)
-        if (NT == P_F16 && rf::env_int("RF_CONV_SKW8", 1) != 0)
-            return gather ? launch_sk<T128w8, E_CONV, NT, true>(p, (int)sk_grid_n, stream, what)
-                          : launch_sk<T128w8, E_CONV, NT, false>(p, (int)sk_grid_n, stream, what);
-        return gather ? launch_sk<T128, E_CONV, NT, true>(p, (int)sk_grid_n, stream, what)
-                      : launch_sk<T128, E_CONV, NT, false>(p, (int)sk_grid_n, stream, what);
-    }
-    if (gather)
-        return big ? launch<T256x128, E_CONV, NT, true>(p, stream, what) : launch<T128, E_CONV, NT, true>(p, stream, what);
-    return big ? launch<T256x128, E_CONV, NT, false>(p, stream, what) : launch<T128, E_CONV, NT, false>(p, stream, what);
+    return launch<C, E_CONV, P_F16, GATHER>(a, stream, what);
 }
 
-// nterm: 3 = bf16x3 hi/lo operands, P_F16 = one fp16 plane per operand (w_lo / in_lo unused)
-static int conv_common(EngineArgs& p, int nterm, bool gather, const void* w_hi, const void* w_lo, int cout, int cout_pad, float* out,
-                       const float* bias, const float* res1, const float* res2, void* p_hi, void* p_lo, int p_ld,
-                       int flags, const float* w_fin, const float* b_fin, int n_fin, float elu_alpha, void* workspace,
-                       int64_t ws_bytes, void* stream, const char* what) {
-    RF_REQUIRE(w_hi && (w_lo || nterm == P_F16), "%s: null weights", what);
+// every branch that launches returns; a plan no branch serves is an error, never a silent no-op
+template <int NT, bool GATHER>
+static int conv_run_t(const ConvPlan& pl, EngineArgs& a, void* workspace, void* stream, const char* what) {
+    [[maybe_unused]] const hipStream_t st = (hipStream_t)stream;
+    [[maybe_unused]] const dim3 g(pl.grid), b(pl.block);
+    if (pl.kernel == RF_CONVK_RING_SK) {
+        if (const int rc = sk_setup(a, workspace, stream)) return rc;
+        if (NT == P_F16 && pl.code == CT_64) return launch_sk<T64c, E_CONV, P_F16, GATHER>(a, pl.grid, stream, what);
+        if (pl.code == CT_128w8) return launch_sk<T128w8, E_CONV, NT, GATHER>(a, pl.grid, stream, what);
+        if (pl.code == CT_128) return launch_sk<T128, E_CONV, NT, GATHER>(a, pl.grid, stream, what);
+    } else if (pl.kernel == RF_CONVK_RING && pl.code == CT_256x128) {
+        return launch<T256x128, E_CONV, NT, GATHER>(a, stream, what);
+    } else if (pl.kernel == RF_CONVK_RING && NT != P_F16) {
+        if (pl.code == CT_128) return launch<T128, E_CONV, NT, GATHER>(a, stream, what);
+    } else if (pl.kernel == RF_CONVK_RING || (pl.kernel == RF_CONVK_RING_HALO && NT == P_F16 && GATHER)) {
+        if (pl.code == CT_256x64) return run_ring_f16<T256x64, GATHER>(pl, a, stream, what);
+        if (pl.code == CT_64) return run_ring_f16<T64c, GATHER>(pl, a, stream, what);
+        if (pl.code == CT_64x128) return run_ring_f16<T64x128c, GATHER>(pl, a, stream, what);
+        if (pl.code == CT_128) return run_ring_f16<T128, GATHER>(pl, a, stream, what);
+        if (pl.code == CT_128w8) return run_ring_f16<T128w8, GATHER>(pl, a, stream, what);
+        if (pl.code == CT_256) return run_ring_f16<T256, GATHER>(pl, a, stream, what);
+    } else if (pl.kernel == RF_CONVK_PHASED && NT == P_F16) {
+        return launch_phased<E_CONV, P_F16, GATHER, 256>(a, stream, what);
+    } else if constexpr (NT == P_F16 && GATHER) {  // the halo-tiled 3x3 kernels: fp16 convolutions only
+        if (pl.kernel == RF_CONVK_HALO2) {
+#ifdef RF_STUDY
+            if (pl.dbg) {  // (5 .. 7 launch nothing)
+                if (pl.dbg == 1) RF_LAUNCH((halo2_kernel<4, 128, 1>), g, b, 0, st, a);
+                if (pl.dbg == 2) RF_LAUNCH((halo2_kernel<4, 128, 2>), g, b, 0, st, a);
+                if (pl.dbg == 3) RF_LAUNCH((halo2_kernel<4, 128, 3>), g, b, 0, st, a);
+                if (pl.dbg == 4) RF_LAUNCH((halo2_kernel<4, 128, 4>), g, b, 0, st, a);
+                if (pl.dbg == 8) RF_LAUNCH((halo2_kernel<4, 128, 8>), g, b, 0, st, a);
+                return rf::check_launch(what);
+            }
+#endif
+            if (pl.code == 3064) RF_LAUNCH((halo2_kernel<3, 64>), g, b, 0, st, a);
+            else if (pl.code == 5064) RF_LAUNCH((halo2_kernel<5, 64>), g, b, 0, st, a);
+            else if (pl.code == 4064) RF_LAUNCH((halo2_kernel<4, 64>), g, b, 0, st, a);
+            else if (pl.code == 3128) RF_LAUNCH((halo2_kernel<3, 128>), g, b, 0, st, a);
+            else if (pl.code == 5128) RF_LAUNCH((halo2_kernel<5, 128>), g, b, 0, st, a);
+            else RF_LAUNCH((halo2_kernel<4, 128>), g, b, 0, st, a);
+            return rf::check_launch(what);
+        }
+        if (pl.kernel == RF_CONVK_HALO3) {
+#ifdef RF_STUDY
+            if (pl.dbg == 1) RF_LAUNCH(halo3_kernel<1>, g, b, 0, st, a);
+            else if (pl.dbg == 2) RF_LAUNCH(halo3_kernel<2>, g, b, 0, st, a);
+            else if (pl.dbg == 4) RF_LAUNCH(halo3_kernel<4>, g, b, 0, st, a);
+            else if (pl.dbg == 6) RF_LAUNCH(halo3_kernel<6>, g, b, 0, st, a);
+            else if (pl.dbg == 8) RF_LAUNCH(halo3_kernel<8>, g, b, 0, st, a);
+            else if (pl.dbg == 14) RF_LAUNCH(halo3_kernel<14>, g, b, 0, st, a);
+            else if (pl.dbg == 15) RF_LAUNCH(halo3_kernel<15>, g, b, 0, st, a);
+            else if (pl.dbg == 30) RF_LAUNCH(halo3_kernel<30>, g, b, 0, st, a);
+            else if (pl.dbg == 16) RF_LAUNCH(halo3_kernel<16>, g, b, 0, st, a);
+            else if (pl.dbg == 32) RF_LAUNCH(halo3_kernel<32>, g, b, 0, st, a);
+            else if (pl.dbg == 64) RF_LAUNCH(halo3_kernel<64>, g, b, 0, st, a);
+            else if (pl.dbg == 96) RF_LAUNCH(halo3_kernel<96>, g, b, 0, st, a);
+            else
+#endif
+            RF_LAUNCH(halo3_kernel<0>, g, b, 0, st, a);
+            return rf::check_launch(what);
+        }
+        if (pl.kernel == RF_CONVK_C32) {
+            RF_LAUNCH(conv3x3_c32_kernel, g, b, 0, st, a);
+            return rf::check_launch(what);
+        }
+#ifdef RF_STUDY
+        if (pl.kernel == RF_CONVK_HK) {
+            RF_LAUNCH(conv3x3_hk_kernel, g, b, 0, st, a);
+            return rf::check_launch(what);
+        }
+#endif
+        if (pl.kernel == RF_CONVK_HS) {
+            if (pl.code == HS_16x32x64) RF_LAUNCH((conv3x3_hs_kernel<16, 32, 64>), g, b, 0, st, a, a.cout / 64);
+            else if (pl.code == HS_16x32x32) RF_LAUNCH((conv3x3_hs_kernel<16, 32, 32>), g, b, 0, st, a, a.cout / 32);
+            else if (pl.code == HS_8x16x64) RF_LAUNCH((conv3x3_hs_kernel<8, 16, 64>), g, b, 0, st, a, a.cout / 64);
+            else RF_LAUNCH((conv3x3_hs_kernel<8, 16, 32>), g, b, 0, st, a, a.cout / 32);
+            return rf::check_launch(what);
+        }
+    }
+    rf::set_error("%s: no kernel serves plan (kernel %d, code %d)", what, pl.kernel, pl.code);
+    return RF_ERR_UNSUPPORTED;
+}
+
+// launch plan pl of the convolution (or, a.deconv set, deconvolution) a
+static int conv_run(const ConvPlan& pl, EngineArgs& a, void* workspace, void* stream, const char* what) {
+    if (pl.refuse) return rf::study_only(pl.refuse);
+    if (pl.kernel == RF_CONVK_NONE) return RF_OK;
+    if (a.plane_f16)
+        return a.deconv ? conv_run_t<P_F16, false>(pl, a, workspace, stream, what)
+                        : conv_run_t<P_F16, true>(pl, a, workspace, stream, what);
+    return a.deconv ? conv_run_t<3, false>(pl, a, workspace, stream, what)
+                    : conv_run_t<3, true>(pl, a, workspace, stream, what);
+}
+
+// Everything about a convolution (deconv_k == 0) or a deconvolution (kernel == stride == deconv_k; cout_pad, kh,
+// kw, stride, pad unused) that is not a pointer, validated: what the four entry points and rf_conv_plan_query share
+static int conv_args(EngineArgs& p, int nterm, int deconv_k, int n_img, int hi, int wi, int cin_pad, int cout,
+                     int cout_pad, int kh, int kw, int stride, int pad, int flags, int n_fin, const char* what) {
+    RF_REQUIRE(cin_pad % BK == 0, "%s: cin_pad %d must be a multiple of %d", what, cin_pad, BK);
+    if (deconv_k > 0) {
+        RF_REQUIRE((deconv_k * deconv_k * cout) % 128 == 0 && cout < 65536, "%s: k*k*cout %% 128", what);
+        p.lda = cin_pad;
+        p.ho = hi;
+        p.wo = wi;
+        p.k = cin_pad;
+        p.deconv = deconv_k;
+        p.n = deconv_k * deconv_k * cout;
+    } else {
+        RF_REQUIRE(kh > 0 && kw > 0 && stride > 0 && pad >= 0, "%s: kernel size and stride must be > 0", what);
+        RF_REQUIRE((cout_pad % 128 == 0 || (nterm == P_F16 && cout_pad == 64)) && cout_pad >= cout,
+                   "%s: cout_pad %d must be %sa multiple of 128", what, cout_pad, nterm == P_F16 ? "64 or " : "");
+        p.hi = hi;
+        p.wi = wi;
+        p.cin_pad = cin_pad;
+        p.cin_m = udiv_magic(cin_pad);
+        p.ho = (hi + 2 * pad - kh) / stride + 1;
+        p.wo = (wi + 2 * pad - kw) / stride + 1;
+        p.kw = kw;
+        p.kw_m = udiv_magic(kw);
+        p.stride = stride;
+        p.pad = pad;
+        p.k = kh * kw * cin_pad;
+        p.n = cout_pad;
+    }
+    RF_REQUIRE(p.k > 0 && p.k < 65536, "%s: kh*kw*cin_pad = %d must be < 65536", what, p.k);
+    p.m = n_img * p.ho * p.wo;
+    p.ldw = p.k;
+    p.plane_f16 = nterm == P_F16;
+    p.cout = cout;
+    p.flags = flags;
+    p.n_fin = n_fin;
     RF_REQUIRE(cout % 4 == 0, "%s: cout must be a multiple of 4", what);
-    RF_REQUIRE(out || p_hi, "%s: no output", what);
-    RF_REQUIRE(!p_hi || ((p_lo || nterm == P_F16) && p_ld % 4 == 0 && p_ld >= cout), "%s: bad plane output", what);
-    RF_REQUIRE(!(flags & RF_CONV_FINAL) || (cout <= 64 && w_fin && b_fin && n_fin > 0 && out),
-               "%s: final head needs cout <= 64 and w_fin/b_fin", what);
+    RF_REQUIRE(!(flags & RF_CONV_FINAL) || (cout <= 64 && n_fin > 0), "%s: final head: cout <= 64, n_fin > 0", what);
     RF_REQUIRE(!(flags & RF_CONV_BORDER_BIAS) ||
-                   (bias && !(flags & RF_CONV_FINAL) && p.kw == 3 && p.k == 9 * p.cin_pad && p.stride == 1 &&
-                    p.pad == 1 && p.ho == p.hi && p.wo == p.wi && p.deconv == 0 && p.ho >= 2 && p.wo >= 2),
-               "%s: RF_CONV_BORDER_BIAS needs a 3x3 stride-1 pad-1 convolution of an image of at least 2 x 2 pixels "
-               "with its 9-row bias", what);
-    static void* z = nullptr;  // device address of the zero row (per process; single device per process)
+                   (!(flags & RF_CONV_FINAL) && conv3x3_same(p) && p.deconv == 0 && p.ho >= 2 && p.wo >= 2),
+               "%s: RF_CONV_BORDER_BIAS needs a non-final 3x3 stride-1 pad-1 convolution of an image of >= 2 x 2 pixels",
+               what);
+    return RF_OK;
+}
+
+// device address of the zero row (per process; single device per process), or null with the error set
+static const bf16_t* zero_row(const char* what) {
+    static void* z = nullptr;
     if (!z && hipGetSymbolAddress(&z, HIP_SYMBOL(g_zero_row)) != hipSuccess) {
         z = nullptr;
         rf::set_error("%s: zero row symbol", what);
-        return RF_ERR_LAUNCH;
     }
-    p.zero = (const bf16_t*)z;
+    return (const bf16_t*)z;
+}
+
+// one convolution or deconvolution call: validate, fill the EngineArgs, plan, launch
+static int conv_common(int nterm, int deconv_k, const void* in_hi, const void* in_lo, int n_img, int hi, int wi, int cin_pad,
+                       const void* w_hi, const void* w_lo, int cout, int cout_pad, int kh, int kw, int stride, int pad,
+                       const float* bias, const float* res1, const float* res2, float* out, void* p_hi, void* p_lo,
+                       int p_ld, int flags, const float* w_fin, const float* b_fin, int n_fin, float elu_alpha,
+                       void* workspace, int64_t ws_bytes, void* stream, const char* what) {
+    const bool f16 = nterm == P_F16;
+    EngineArgs p{};
+    RF_REQUIRE(in_hi && (in_lo || f16), "%s: null input", what);
+    if (const int rc = conv_args(p, nterm, deconv_k, n_img, hi, wi, cin_pad, cout, cout_pad, kh, kw, stride, pad, flags,
+                                 n_fin, what))
+        return rc;
+    RF_REQUIRE(w_hi && (w_lo || f16), "%s: null weights", what);
+    RF_REQUIRE(out || p_hi, "%s: no output", what);
+    RF_REQUIRE(!p_hi || ((p_lo || f16) && p_ld % 4 == 0 && p_ld >= cout), "%s: bad plane output", what);
+    RF_REQUIRE(!(flags & RF_CONV_FINAL) || (w_fin && b_fin && out), "%s: final head needs w_fin/b_fin and out", what);
+    RF_REQUIRE(!(flags & RF_CONV_BORDER_BIAS) || bias, "%s: RF_CONV_BORDER_BIAS needs its 9-row bias", what);
+    if (!(p.zero = zero_row(what))) return RF_ERR_LAUNCH;
+    p.a = (const bf16_t*)in_hi;
+    p.a_lo = (const bf16_t*)in_lo;
     p.w = (const bf16_t*)w_hi;
     p.w_lo = (const bf16_t*)w_lo;
-    p.n = cout_pad;
     p.c = out;
     p.bias = bias;
     p.res1 = res1;
@@ -4512,53 +4628,12 @@ static int conv_common(EngineArgs& p, int nterm, bool gather, const void* w_hi, 
     p.p_hi = (bf16_t*)p_hi;
     p.p_lo = (bf16_t*)p_lo;
     p.p_ld = p_ld;
-    p.plane_f16 = nterm == P_F16;
-    p.range = (p_hi && nterm == P_F16) ? rf::range_word() : nullptr;
-    p.cout = cout;
-    p.flags = flags;
+    p.range = (p_hi && f16) ? rf::range_word() : nullptr;
     p.w_fin = w_fin;
     p.b_fin = b_fin;
-    p.n_fin = n_fin;
     p.elu_alpha = elu_alpha;
-    if (p.m <= 0) return RF_OK;
-    // 256x128 (8 waves) halves the L2 traffic per FLOP of the 128x128 tile but runs one block per CU:
-    // use it only when it still yields >= one tile per CU.
-    const bool big = rf::env_set("RF_CONV_TILE") ? conv_tile_env() == CT_256 : ((p.m + 255) / 256) * (p.n / 128) >= 256;
-    // Too few 128x128 tiles for 256 CUs (one bf16x3 block per CU): stream-K over the K loop, each block
-    // keeping >= 8 K-steps.
-    int64_t skg = 0;
-    int ct = conv_tile_env();
-    // images too small for the 16 x 32 x 128 halo blocks: the right-sized halo kernel, ahead of the small-level
-    // tiles and the stream-K split below (all gathered engine launches)
-    if (nterm == P_F16 && gather && !hk_ok(p) && !halo3_ok(p) && !halo2_ok(p)) {
-        if (const int hs = hs_pick(p)) return launch_hs(p, hs, stream, what);
-    }
-    // small DPT levels (<= 4,096 output pixels per launch: the 64^2 / 32^2 refinenets and their rn convs): the
-    // 64x64 tile, data-parallel at K <= 2,304 and stream-K above (GPU time per launch, rocprofv3 over
-    // tools/kbench.py conv: 256->256 @32 32.4 -> 26.6 us, @64 30.1 -> 27.6 us, 1024->256 @32 50.4 -> 41.4 us;
-    // 1024->256 @64 stays on the default, 54.4 vs 68.1 us).  RF_CONV_SMALL=0 keeps the default tiles.
-    if (!ct && RF_ENV_ONCE("RF_CONV_SMALL", 1) != 0 && nterm == P_F16 && gather && p.kw == 3 && p.n % 64 == 0 && p.m <= 4096 &&
-        (p.k <= 2304 || p.m <= 1024))
-        ct = p.k <= 2304 ? CT_64 : CT_64SK;
-    if (nterm == P_F16 && ct == CT_64SK && p.n % 64 == 0 && workspace && ws_bytes >= SK_WS_BYTES) {
-        // A/B: stream-K over the 64x64 small-level tile, up to two blocks per CU, >= 12 K-steps per block
-        const int64_t tiles = (int64_t)((p.m + 63) / 64) * (p.n / 64);
-        const int64_t grid = std::min<int64_t>(512, tiles * (p.k / BK) / 12);
-        if (grid > tiles) {
-            if (const int rc = sk_setup(p, workspace, stream)) return rc;
-            return gather ? launch_sk<T64c, E_CONV, P_F16, true>(p, (int)grid, stream, what)
-                          : launch_sk<T64c, E_CONV, P_F16, false>(p, (int)grid, stream, what);
-        }
-    }
-    if (!big && p.n % 128 == 0 && workspace && ws_bytes >= SK_WS_BYTES && rf::env_int("RF_CONV_SK", 1) != 0 &&
-        !(nterm == P_F16 && (ct == CT_64 || ct == CT_64x128 || ct == CT_64SK))) {
-        const int64_t tiles = (int64_t)((p.m + 127) / 128) * (p.n / 128);
-        const int64_t work = tiles * (p.k / BK);
-        const int64_t grid = std::min<int64_t>(256, work / 8);
-        if (tiles < 192 && grid > tiles) skg = grid;
-    }
-    return nterm == P_F16 ? conv_dispatch<P_F16>(p, gather, big, skg, workspace, stream, what, ct == CT_64 ? CT_64 : CT_AUTO)
-                          : conv_dispatch<3>(p, gather, big, skg, workspace, stream, what);
+    const ConvPlan pl = conv_plan(p, nterm, deconv_k == 0, workspace && ws_bytes >= SK_WS_BYTES);
+    return conv_run(pl, p, workspace, stream, what);
 }
 
 extern "C" int rf_conv2d_bf16x3(const void* in_hi, const void* in_lo, int n_img, int hi, int wi, int cin_pad,
@@ -4566,29 +4641,9 @@ extern "C" int rf_conv2d_bf16x3(const void* in_hi, const void* in_lo, int n_img,
                                 int pad, const float* bias, const float* res1, const float* res2, float* out,
                                 void* p_hi, void* p_lo, int p_ld, int flags, const float* w_fin, const float* b_fin,
                                 int n_fin, float elu_alpha, void* workspace, int64_t ws_bytes, void* stream) {
-    RF_REQUIRE(in_hi && in_lo, "rf_conv2d_bf16x3: null input");
-    RF_REQUIRE(cin_pad % BK == 0, "rf_conv2d_bf16x3: cin_pad %d must be a multiple of %d", cin_pad, BK);
-    RF_REQUIRE(cout_pad % 128 == 0 && cout_pad >= cout, "rf_conv2d_bf16x3: cout_pad %d must be a multiple of 128",
-               cout_pad);
-    EngineArgs p{};
-    p.a = (const bf16_t*)in_hi;
-    p.a_lo = (const bf16_t*)in_lo;
-    p.hi = hi;
-    p.wi = wi;
-    p.cin_pad = cin_pad;
-    p.cin_m = udiv_magic(cin_pad);
-    p.ho = (hi + 2 * pad - kh) / stride + 1;
-    p.wo = (wi + 2 * pad - kw) / stride + 1;
-    p.kw = kw;
-    p.kw_m = udiv_magic(kw);
-    p.stride = stride;
-    p.pad = pad;
-    p.m = n_img * p.ho * p.wo;
-    p.k = kh * kw * cin_pad;
-    RF_REQUIRE(p.k < 65536, "conv: kh*kw*cin_pad = %d must be < 65536", p.k);
-    p.ldw = p.k;
-    return conv_common(p, 3, true, w_hi, w_lo, cout, cout_pad, out, bias, res1, res2, p_hi, p_lo, p_ld, flags, w_fin,
-                       b_fin, n_fin, elu_alpha, workspace, ws_bytes, stream, "rf_conv2d_bf16x3");
+    return conv_common(3, 0, in_hi, in_lo, n_img, hi, wi, cin_pad, w_hi, w_lo, cout, cout_pad, kh, kw, stride, pad, bias,
+                       res1, res2, out, p_hi, p_lo, p_ld, flags, w_fin, b_fin, n_fin, elu_alpha, workspace, ws_bytes,
+                       stream, "rf_conv2d_bf16x3");
 }
 
 extern "C" int rf_conv2d_f16(const void* in, int n_img, int hi, int wi, int cin_pad, const void* w, int cout,
@@ -4596,83 +4651,67 @@ extern "C" int rf_conv2d_f16(const void* in, int n_img, int hi, int wi, int cin_
                              const float* res2, float* out, void* p_out, int p_ld, int flags, const float* w_fin,
                              const float* b_fin, int n_fin, float elu_alpha, void* workspace, int64_t ws_bytes,
                              void* stream) {
-    RF_REQUIRE(in, "rf_conv2d_f16: null input");
-    RF_REQUIRE(cin_pad % BK == 0, "rf_conv2d_f16: cin_pad %d must be a multiple of %d", cin_pad, BK);
-    RF_REQUIRE((cout_pad % 128 == 0 || cout_pad == 64) && cout_pad >= cout,
-               "rf_conv2d_f16: cout_pad %d must be 64 or a multiple of 128", cout_pad);
-    EngineArgs p{};
-    p.a = (const bf16_t*)in;
-    p.hi = hi;
-    p.wi = wi;
-    p.cin_pad = cin_pad;
-    p.cin_m = udiv_magic(cin_pad);
-    p.ho = (hi + 2 * pad - kh) / stride + 1;
-    p.wo = (wi + 2 * pad - kw) / stride + 1;
-    p.kw = kw;
-    p.kw_m = udiv_magic(kw);
-    p.stride = stride;
-    p.pad = pad;
-    p.m = n_img * p.ho * p.wo;
-    p.k = kh * kw * cin_pad;
-    RF_REQUIRE(p.k < 65536, "conv: kh*kw*cin_pad = %d must be < 65536", p.k);
-    p.ldw = p.k;
-    return conv_common(p, P_F16, true, w, nullptr, cout, cout_pad, out, bias, res1, res2, p_out, nullptr, p_ld, flags,
-                       w_fin, b_fin, n_fin, elu_alpha, workspace, ws_bytes, stream, "rf_conv2d_f16");
+    return conv_common(P_F16, 0, in, nullptr, n_img, hi, wi, cin_pad, w, nullptr, cout, cout_pad, kh, kw, stride, pad,
+                       bias, res1, res2, out, p_out, nullptr, p_ld, flags, w_fin, b_fin, n_fin, elu_alpha, workspace,
+                       ws_bytes, stream, "rf_conv2d_f16");
 }
 
-// one grouped-launch member: the fields rf_conv2d_f16 / rf_deconv2d_f16 and conv_common set (the deconvolution
-// runs its dense A as a 1x1 gather: the same row addresses), or an error message
-static const char* group_member(EngineArgs& p, const rf_conv_desc& d, const void* zero) {
-    if (!d.in || !d.w || !(d.out || d.p_out)) return "null pointer";
-    if (d.cin_pad % BK) return "cin_pad must be a multiple of 32";
-    if (d.cout % 4) return "cout must be a multiple of 4";
-    if (d.p_out && (d.p_ld % 4 || d.p_ld < d.cout)) return "bad p_ld";
-    if (d.flags & RF_CONV_FINAL) return "the fused final head runs on its own launch";
+extern "C" int rf_deconv2d_bf16x3(const void* in_hi, const void* in_lo, int n_img, int hi, int wi, int cin_pad,
+                                  const void* w_hi, const void* w_lo, int cout, int k, const float* bias, float* out,
+                                  void* p_hi, void* p_lo, int p_ld, void* workspace, int64_t ws_bytes, void* stream) {
+    return conv_common(3, k, in_hi, in_lo, n_img, hi, wi, cin_pad, w_hi, w_lo, cout, 0, 0, 0, 0, 0, bias, nullptr, nullptr,
+                       out, p_hi, p_lo, p_ld, 0, nullptr, nullptr, 0, 0.f, workspace, ws_bytes, stream,
+                       "rf_deconv2d_bf16x3");
+}
+
+extern "C" int rf_deconv2d_f16(const void* in, int n_img, int hi, int wi, int cin_pad, const void* w, int cout, int k,
+                               const float* bias, float* out, void* p_out, int p_ld, void* workspace, int64_t ws_bytes,
+                               void* stream) {
+    return conv_common(P_F16, k, in, nullptr, n_img, hi, wi, cin_pad, w, nullptr, cout, 0, 0, 0, 0, 0, bias, nullptr,
+                       nullptr, out, p_out, nullptr, p_ld, 0, nullptr, nullptr, 0, 0.f, workspace, ws_bytes, stream,
+                       "rf_deconv2d_f16");
+}
+
+extern "C" int rf_conv_plan_query(int operand, int deconv_k, int n_img, int hi, int wi, int cin_pad, int cout,
+                                  int cout_pad, int kh, int kw, int stride, int pad, int flags, int n_fin,
+                                  int64_t ws_bytes, rf_conv_plan* out) {
+    RF_REQUIRE(out && (operand == RF_DT_F16 || operand == RF_DT_BF16) && deconv_k >= 0,
+               "rf_conv_plan_query: null output, or operand / deconv_k out of range");
+    EngineArgs p{};
+    const int nterm = operand == RF_DT_F16 ? P_F16 : 3;
+    if (const int rc = conv_args(p, nterm, deconv_k, n_img, hi, wi, cin_pad, cout, cout_pad, kh, kw, stride, pad, flags,
+                                 n_fin, "rf_conv_plan_query"))
+        return rc;
+    const ConvPlan pl = conv_plan(p, nterm, deconv_k == 0, ws_bytes >= SK_WS_BYTES);
+    *out = rf_conv_plan{pl.kernel, pl.code, pl.grid, pl.block, pl.halo_lg, pl.dbg, pl.refuse != nullptr};
+    return RF_OK;
+}
+
+// one grouped-launch member: the fields rf_conv2d_f16 sets; a deconvolution runs its dense A as a 1x1 gather (the
+// same row addresses) over its k*k*cout filters
+static int group_member(EngineArgs& p, const rf_conv_desc& d, const void* zero, const char* what) {
+    const int dk = d.deconv_k > 0 ? d.deconv_k : 0, n = dk ? dk * dk * d.cout : d.cout_pad;
+    RF_REQUIRE(d.in && d.w && (d.out || d.p_out), "%s: null pointer", what);
+    RF_REQUIRE(!d.p_out || (d.p_ld % 4 == 0 && d.p_ld >= d.cout), "%s: bad p_ld", what);
+    RF_REQUIRE(!(d.flags & RF_CONV_FINAL), "%s: the fused final head runs on its own launch", what);
+    RF_REQUIRE(!dk || !d.flags, "%s: a deconvolution takes no flags", what);
+    RF_REQUIRE(!(d.flags & RF_CONV_BORDER_BIAS) || d.bias, "%s: RF_CONV_BORDER_BIAS needs its 9-row bias", what);
+    RF_REQUIRE(n % T128w8::BN == 0, "%s: output channels (a deconvolution's k*k*cout) must be a multiple of 128", what);
     p = EngineArgs{};
+    if (const int rc = dk ? conv_args(p, P_F16, 0, d.n_img, d.hi, d.wi, d.cin_pad, d.cout, n, 1, 1, 1, 0, 0, 0, what)
+                          : conv_args(p, P_F16, 0, d.n_img, d.hi, d.wi, d.cin_pad, d.cout, n, d.kh, d.kw, d.stride, d.pad,
+                                      d.flags, 0, what))
+        return rc;
+    p.deconv = dk;
     p.a = (const bf16_t*)d.in;
-    p.cin_pad = d.cin_pad;
-    p.cin_m = udiv_magic(d.cin_pad);
     p.zero = (const bf16_t*)zero;
-    if (d.deconv_k > 0) {
-        p.hi = p.ho = d.hi;
-        p.wi = p.wo = d.wi;
-        p.kw = 1;
-        p.stride = 1;
-        p.pad = 0;
-        p.deconv = d.deconv_k;
-        p.n = d.deconv_k * d.deconv_k * d.cout;
-        if (d.flags) return "a deconvolution takes no flags";
-    } else {
-        p.hi = d.hi;
-        p.wi = d.wi;
-        p.ho = (d.hi + 2 * d.pad - d.kh) / d.stride + 1;
-        p.wo = (d.wi + 2 * d.pad - d.kw) / d.stride + 1;
-        p.kw = d.kw;
-        p.stride = d.stride;
-        p.pad = d.pad;
-        p.n = d.cout_pad;
-        if (d.cout_pad < d.cout) return "cout_pad < cout";
-        if ((d.flags & RF_CONV_BORDER_BIAS) &&
-            !(d.bias && d.kh == 3 && d.kw == 3 && d.stride == 1 && d.pad == 1 && d.hi >= 2 && d.wi >= 2))
-            return "RF_CONV_BORDER_BIAS needs a 3x3 stride-1 pad-1 convolution of an image of at least 2 x 2 pixels "
-                   "with its 9-row bias";
-    }
-    p.kw_m = udiv_magic(p.kw);
-    p.m = d.n_img * p.ho * p.wo;
-    p.k = (d.deconv_k > 0 ? 1 : d.kh * d.kw) * d.cin_pad;
-    if (p.k >= 65536) return "kh*kw*cin_pad must be < 65536";
-    if (p.n % T128w8::BN) return "output channels (k*k*cout for a deconvolution) must be a multiple of 128";
-    p.ldw = p.k;
     p.w = (const bf16_t*)d.w;
     p.c = d.out;
     p.bias = d.bias;
     p.p_hi = (bf16_t*)d.p_out;
     p.p_ld = d.p_ld;
-    p.plane_f16 = 1;
     p.range = d.p_out ? rf::range_word() : nullptr;
-    p.cout = d.cout;
-    p.flags = d.flags;
-    return nullptr;
+    return RF_OK;
 }
 
 // dense: every member is a 1x1 stride-1 convolution over unpadded pixels (A = dense rows of cin_pad, K a
@@ -4681,19 +4720,16 @@ static const char* group_member(EngineArgs& p, const rf_conv_desc& d, const void
 template <bool DENSE>
 static int conv_group_launch(int n_conv, const rf_conv_desc* convs, void* stream, const char* what) {
     RF_REQUIRE(n_conv >= 1 && n_conv <= GROUP_MAX && convs, "%s: 1..%d convolutions", what, GROUP_MAX);
-    static void* z = nullptr;
-    if (!z && hipGetSymbolAddress(&z, HIP_SYMBOL(g_zero_row)) != hipSuccess) {
-        z = nullptr;
-        rf::set_error("%s: zero row symbol", what);
-        return RF_ERR_LAUNCH;
-    }
+    const bf16_t* z = zero_row(what);
+    if (!z) return RF_ERR_LAUNCH;
     using C = std::conditional_t<DENSE, T128w8k2s4, T128w8>;
     GroupArgs g{};
     g.n = n_conv;
     int blocks = 0;
     for (int q = 0; q < n_conv; ++q) {
-        const char* err = group_member(g.p[q], convs[q], z);
-        RF_REQUIRE(!err, "%s: conv %d: %s", what, q, err ? err : "");
+        char who[64];
+        snprintf(who, sizeof(who), "%s: conv %d", what, q);
+        if (const int rc = group_member(g.p[q], convs[q], z, who)) return rc;
         EngineArgs& p = g.p[q];
         if constexpr (DENSE) {
             RF_REQUIRE(convs[q].kh == 1 && convs[q].kw == 1 && convs[q].stride == 1 && convs[q].pad == 0 &&
@@ -4742,43 +4778,4 @@ extern "C" int rf_conv1x1_f16_group(int n_conv, const void* const* in, const int
     for (int q = 0; q < n_conv; ++q) ok = ok && cin_pad[q] % 64 == 0;
     return ok ? conv_group_launch<true>(n_conv, d, stream, "rf_conv1x1_f16_group")
               : conv_group_launch<false>(n_conv, d, stream, "rf_conv1x1_f16_group");
-}
-
-extern "C" int rf_deconv2d_bf16x3(const void* in_hi, const void* in_lo, int n_img, int hi, int wi, int cin_pad,
-                                  const void* w_hi, const void* w_lo, int cout, int k, const float* bias, float* out,
-                                  void* p_hi, void* p_lo, int p_ld, void* workspace, int64_t ws_bytes, void* stream) {
-    RF_REQUIRE(in_hi && in_lo, "rf_deconv2d_bf16x3: null input");
-    RF_REQUIRE(cin_pad % BK == 0, "rf_deconv2d_bf16x3: cin_pad must be a multiple of %d", BK);
-    RF_REQUIRE((k * k * cout) % 128 == 0 && cout < 65536, "rf_deconv2d_bf16x3: k*k*cout must be a multiple of 128");
-    EngineArgs p{};
-    p.a = (const bf16_t*)in_hi;
-    p.a_lo = (const bf16_t*)in_lo;
-    p.lda = cin_pad;
-    p.ho = hi;
-    p.wo = wi;
-    p.m = n_img * hi * wi;
-    p.k = cin_pad;
-    p.ldw = cin_pad;
-    p.deconv = k;
-    return conv_common(p, 3, false, w_hi, w_lo, cout, k * k * cout, out, bias, nullptr, nullptr, p_hi, p_lo, p_ld, 0,
-                       nullptr, nullptr, 0, 0.f, workspace, ws_bytes, stream, "rf_deconv2d_bf16x3");
-}
-
-extern "C" int rf_deconv2d_f16(const void* in, int n_img, int hi, int wi, int cin_pad, const void* w, int cout, int k,
-                               const float* bias, float* out, void* p_out, int p_ld, void* workspace, int64_t ws_bytes,
-                               void* stream) {
-    RF_REQUIRE(in, "rf_deconv2d_f16: null input");
-    RF_REQUIRE(cin_pad % BK == 0, "rf_deconv2d_f16: cin_pad must be a multiple of %d", BK);
-    RF_REQUIRE((k * k * cout) % 128 == 0 && cout < 65536, "rf_deconv2d_f16: k*k*cout must be a multiple of 128");
-    EngineArgs p{};
-    p.a = (const bf16_t*)in;
-    p.lda = cin_pad;
-    p.ho = hi;
-    p.wo = wi;
-    p.m = n_img * hi * wi;
-    p.k = cin_pad;
-    p.ldw = cin_pad;
-    p.deconv = k;
-    return conv_common(p, P_F16, false, w, nullptr, cout, k * k * cout, out, bias, nullptr, nullptr, p_out, nullptr,
-                       p_ld, 0, nullptr, nullptr, 0, 0.f, workspace, ws_bytes, stream, "rf_deconv2d_f16");
 }

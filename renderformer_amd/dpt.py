@@ -273,6 +273,19 @@ class _Conv:
                  ptr(ws), ws.numel(), stream())
         return out, pl
 
+    def plan(self, x: Planes, stride=1, pad=None, res1=None, res2=None, out_f32=False, planes_ld=None,
+             planes_silu=False, final=None, final_flags=0, border_bias=None):
+        """The kernel ``self(x, ...)`` with these arguments (``__call__``'s) launches under the current RF_CONV_*
+        environment (``_lib.ConvPlan``; tests and tools assert it before they compare kernels)."""
+        from . import _lib
+        n, h, w, _ = x.shape
+        flags = (FINAL | final_flags) if final is not None else (PLANE_SILU if planes_silu else 0)
+        if border_bias is not None:
+            flags |= BORDER_BIAS
+        return _lib.conv_plan(self.f16, n, h, w, self.cin_pad, self.cout, self.cout_pad, self.kh, self.kw, stride,
+                              self.kh // 2 if pad is None else pad, flags, final[0].shape[0] if final else 0, self.k,
+                              int(_lib.load(require_device=False).rf_gemm_workspace_bytes()))
+
 
 PRECISIONS = ("f16", "bf16x3")
 

@@ -2,7 +2,8 @@
 (RF_CONV_HALO_SMALL, default 1; 0 = the gathered engine launches; a geometry code forces one block geometry).
 Tolerances are test_kernels_gpu.py::test_conv_halo3's: against an fp64 convolution of the same fp16-rounded operands,
 fp32 output < 2e-5, SiLU fp16 planes < 1e-3, padded plane columns exactly zero; against the gathered engine kernel on
-the same operands (same products, another fp32 summation order) < 1e-6."""
+the same operands (same products, another fp32 summation order) < 1e-6.  Every case asks the planner
+(rf_conv_plan_query) which kernel and block geometry its call launches before it launches it."""
 import math
 
 import pytest
@@ -70,6 +71,12 @@ def test_conv_halo_small(cin, cout, hh, ww, n_img, knob, monkeypatch):
     def fused():
         return conv(xs_silu, res1=r1.to(dev), res2=r2.to(dev), out_f32=True, planes_ld=cout + 32, planes_silu=True)
 
+    def planned(kernels, code=None):
+        from renderformer_amd._lib import CONVK
+        for p in (conv.plan(xs_silu, planes_silu=True), conv.plan(xs)):
+            assert p.kernel in [CONVK[k] for k in kernels] and code in (None, p.code) and not p.refuse, p
+
+    planned(["hs"], int(knob) if knob != "1" else 163232 if hh == 128 else 81632)  # (the geometries CASES names)
     out, pl = fused()
     sx = _h(F.silu(x.double()).float())
     ref = F.conv2d(sx, _h(w), b.double(), padding=1).permute(0, 2, 3, 1) + r1 + r2
@@ -78,6 +85,7 @@ def test_conv_halo_small(cin, cout, hh, ww, n_img, knob, monkeypatch):
     ref2 = F.conv2d(_h(x), _h(w), b.double(), padding=1).permute(0, 2, 3, 1)
     e_out2 = relerr(out2.cpu(), ref2)
     monkeypatch.setenv("RF_CONV_HALO_SMALL", "0")  # the gathered engine kernel on the same operands
+    planned(["ring", "ring_sk"])
     out3, pl3 = fused()
     out4, _ = conv(xs, out_f32=True)
     e_eng, e_eng2 = relerr(out.cpu(), out3.cpu()), relerr(out2.cpu(), out4.cpu())

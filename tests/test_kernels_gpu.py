@@ -1031,13 +1031,26 @@ def _planes_value(pl):
     return pl.hi.float() if pl.f16 else pl.hi.float() + pl.lo.float()
 
 
+def _plan_is(conv, xs, family, code=None, **kw):
+    """conv(xs, **kw) under the environment as it stands launches a kernel of `family` (a key of _lib.CONVK; several
+    separated by "|") and, if given, variant `code`: asked of the planner (rf_conv_plan_query) before the launch, so a
+    test that names a kernel cannot pass on another one."""
+    from renderformer_amd._lib import CONVK
+    p = conv.plan(xs, **kw)
+    assert p.kernel in [CONVK[f] for f in family.split("|")] and code in (None, p.code) and not p.refuse, (family, code, p)
+    return p
+
+
 @pytest.mark.parametrize("tile", ["auto", "4w", "64", "6412", "6464"])
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("cin,cout,k,stride,hw", [(64, 128, 3, 1, 17), (256, 256, 3, 1, 32), (16, 32, 3, 1, 20),
                                                    (1024, 128, 1, 1, 16), (128, 128, 3, 2, 16), (48, 200, 3, 1, 9)])
 def test_conv_matches_fp64(cin, cout, k, stride, hw, prec, tile, monkeypatch):
-    """auto: small grids on the 8-wave 128x128 tile (data-parallel or stream-K); 4w: the 4-wave tile; 64 / 6412:
-    the data-parallel 64x64 / 64x128 small-level tiles, 6464: stream-K over the 64x64 tile (fp16 only)."""
+    """auto: the host's choice -- bf16x3 on the 4-wave 128x128 tile (data-parallel or stream-K), fp16 on the small-level
+    64x64 tile, conv3x3_hs_kernel (the 3x3 same-size shape with a multiple of 32 filters) or, the 1x1, stream-K over
+    the 8-wave 128x128 tile; 4w: the 4-wave tile; 64 / 6412: the data-parallel 64x64 / 64x128 small-level tiles, 6464:
+    stream-K over the 64x64 tile (fp16 only).  An fp16 bank of <= 64 filters runs on the 256x64 tile whatever the
+    knob says.  Each case asserts that plan before it launches."""
     if tile in ("64", "6412", "6464") and prec != "f16":
         pytest.skip("the small-level tiles serve fp16 operands")
     if tile == "4w":
@@ -1055,7 +1068,13 @@ def test_conv_matches_fp64(cin, cout, k, stride, hw, prec, tile, monkeypatch):
     xn = x.permute(0, 2, 3, 1).contiguous().to(dev)
     pad = k // 2
     ref = F.conv2d(_q(x, prec), _q(w, prec), b.double(), stride=stride, padding=pad).permute(0, 2, 3, 1)
-    out, _ = conv(split_planes(xn, conv.cin_pad, f16=f16), stride=stride, pad=pad, out_f32=True)
+    xs = split_planes(xn, conv.cin_pad, f16=f16)
+    auto_f16 = {64: ("ring", 64), 256: ("hs", 81632), 1024: ("ring_sk", 1288), 128: ("ring", 64), 48: ("ring", 64)}
+    want = (("ring", 25664) if f16 and cout <= 64 else auto_f16[cin] if f16 and tile == "auto" else
+            {"auto": ("ring|ring_sk", 128), "4w": ("ring|ring_sk", 128), "64": ("ring", 64), "6412": ("ring", 6412),
+             "6464": ("ring_sk", 64)}[tile])
+    _plan_is(conv, xs, *want, stride=stride, pad=pad)
+    out, _ = conv(xs, stride=stride, pad=pad, out_f32=True)
     assert relerr(out.cpu(), ref) < 2e-5
     if f16:  # and the fp16 rounding itself stays small against the exact fp64 convolution
         exact = F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=pad).permute(0, 2, 3, 1)
@@ -1095,8 +1114,9 @@ def test_conv_halo(cin, cout, hw, tile, monkeypatch):
     xn = x.permute(0, 2, 3, 1).contiguous().to(dev)
     r1 = torch.randn(2, hw, hw, cout, generator=g)
     r2 = torch.randn(2, hw, hw, cout, generator=g)
-    out, pl = conv(split_planes(xn, conv.cin_pad, silu=True, f16=True), res1=r1.to(dev), res2=r2.to(dev),
-                   out_f32=True, planes_ld=cout, planes_silu=True)
+    xs = split_planes(xn, conv.cin_pad, silu=True, f16=True)
+    _plan_is(conv, xs, "ring_halo", 25664 if tile == "64" else int(tile), planes_silu=True)
+    out, pl = conv(xs, res1=r1.to(dev), res2=r2.to(dev), out_f32=True, planes_ld=cout, planes_silu=True)
     sx = _q(F.silu(x.double()).float(), "f16")
     ref = F.conv2d(sx, _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1) + r1 + r2
     assert relerr(out.cpu(), ref) < 2e-5
@@ -1126,30 +1146,39 @@ def test_conv_halo2(cin, cout, hh, ww, n_img, h2s, monkeypatch):
     xn = x.permute(0, 2, 3, 1).contiguous().to(dev)
     r1 = torch.randn(n_img, hh, ww, cout, generator=g)
     r2 = torch.randn(n_img, hh, ww, cout, generator=g)
-    out, pl = conv(split_planes(xn, conv.cin_pad, silu=True, f16=True), res1=r1.to(dev), res2=r2.to(dev),
-                   out_f32=True, planes_ld=cout + 32, planes_silu=True)
+    xs_silu, xs = split_planes(xn, conv.cin_pad, silu=True, f16=True), split_planes(xn, conv.cin_pad, f16=True)
+    for a, kw in ((xs_silu, dict(planes_silu=True)), (xs, {})):  # the W ring depth and the 64- / 128-channel block
+        _plan_is(conv, a, "halo2", 1000 * int(h2s) + (64 if cout <= 64 else 128), **kw)
+    out, pl = conv(xs_silu, res1=r1.to(dev), res2=r2.to(dev), out_f32=True, planes_ld=cout + 32, planes_silu=True)
     sx = _q(F.silu(x.double()).float(), "f16")
     ref = F.conv2d(sx, _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1) + r1 + r2
     assert relerr(out.cpu(), ref) < 2e-5
     assert relerr(_planes_value(pl)[..., :cout].cpu(), F.silu(ref)) < 1e-3
     assert (pl.hi[..., cout:] == 0).all()
     # plain output (no residuals): the same kernel against the unfused conv
-    out2, _ = conv(split_planes(xn, conv.cin_pad, f16=True), out_f32=True)
+    out2, _ = conv(xs, out_f32=True)
     ref2 = F.conv2d(_q(x, "f16"), _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1)
     assert relerr(out2.cpu(), ref2) < 2e-5
 
 
 @pytest.mark.parametrize("cin,cout,hh,ww,n_img", [(256, 128, 32, 64, 2), (128, 256, 48, 32, 1), (32, 128, 16, 32, 3),
                                                   (96, 128, 16, 96, 1), (256, 256, 64, 64, 1), (64, 384, 16, 32, 1),
-                                                  (512, 128, 16, 32, 1)])
+                                                  (512, 128, 16, 32, 1), (512, 128, 16, 32, 3)])
 def test_conv_halo3(cin, cout, hh, ww, n_img, monkeypatch):
     """halo3_kernel (the default for the 512^2 / 256^2 DPT convs with a multiple of 128 filters: the bank read from L2
     into a register ring, one barrier per 32-channel chunk): 1 to 16 channel chunks (the last chunk re-stages its own
     halo and the last taps re-load the last W slice), several images, tiles along both axes, 1 to 3 channel tiles,
     fused bias + 2 residuals + SiLU fp16 planes with a padded row stride, and the plain fp32 output; against fp64 on
-    the same fp16 operands and against halo2 (same products, fp32 summation order)."""
+    the same fp16 operands and against halo2 (same products, fp32 summation order).
+    The planner is asked before each launch.  It showed that (512, 128, 16, 32, 1), the 16-chunk case, never ran
+    halo3: at K > 2,304 and <= 1,024 pixels the small-level rule sends it to the 64x64 stream-K tile first (and that
+    kernel was compared with itself).  The case stays, asserting what it runs; (512, 128, 16, 32, 3) with
+    RF_CONV_SK=0 is the nearest shape on which halo3 / halo2 do run 16 chunks."""
     monkeypatch.setenv("RF_CONV_HALO2", "1")
     monkeypatch.setenv("RF_CONV_HALO3", "1")
+    small_sk = (cin, n_img) == (512, 1)
+    if (cin, n_img) == (512, 3):
+        monkeypatch.setenv("RF_CONV_SK", "0")  # (else the 128x128 stream-K split takes its 12 tiles)
     from renderformer_amd.dpt import _Conv, split_planes
     g = torch.Generator(device="cpu").manual_seed(cin * hh + cout + ww + 11)
     w = torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9)
@@ -1159,18 +1188,21 @@ def test_conv_halo3(cin, cout, hh, ww, n_img, monkeypatch):
     xn = x.permute(0, 2, 3, 1).contiguous().to(dev)
     r1 = torch.randn(n_img, hh, ww, cout, generator=g)
     r2 = torch.randn(n_img, hh, ww, cout, generator=g)
-    out, pl = conv(split_planes(xn, conv.cin_pad, silu=True, f16=True), res1=r1.to(dev), res2=r2.to(dev),
-                   out_f32=True, planes_ld=cout + 32, planes_silu=True)
+    xs_silu, xs = split_planes(xn, conv.cin_pad, silu=True, f16=True), split_planes(xn, conv.cin_pad, f16=True)
+    _plan_is(conv, xs_silu, *(("ring_sk", 64) if small_sk else ("halo3", 0)), planes_silu=True)
+    out, pl = conv(xs_silu, res1=r1.to(dev), res2=r2.to(dev), out_f32=True, planes_ld=cout + 32, planes_silu=True)
     sx = _q(F.silu(x.double()).float(), "f16")
     ref = F.conv2d(sx, _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1) + r1 + r2
     assert relerr(out.cpu(), ref) < 2e-5
     assert relerr(_planes_value(pl)[..., :cout].cpu(), F.silu(ref)) < 1e-3
     assert (pl.hi[..., cout:] == 0).all()
-    out2, _ = conv(split_planes(xn, conv.cin_pad, f16=True), out_f32=True)
+    _plan_is(conv, xs, *(("ring_sk", 64) if small_sk else ("halo3", 0)))
+    out2, _ = conv(xs, out_f32=True)
     ref2 = F.conv2d(_q(x, "f16"), _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1)
     assert relerr(out2.cpu(), ref2) < 2e-5
     monkeypatch.setenv("RF_CONV_HALO3", "0")  # halo2 on the same operands
-    out3, _ = conv(split_planes(xn, conv.cin_pad, f16=True), out_f32=True)
+    _plan_is(conv, xs, *(("ring_sk", 64) if small_sk else ("halo2", 4128)))
+    out3, _ = conv(xs, out_f32=True)
     assert relerr(out3.cpu(), out2.cpu().double()) < 1e-6
 
 
@@ -1192,21 +1224,24 @@ def test_conv_hk(cin, cout, hh, ww, n_img, monkeypatch):
     xn = x.permute(0, 2, 3, 1).contiguous().to(dev)
     r1 = torch.randn(n_img, hh, ww, cout, generator=g)
     r2 = torch.randn(n_img, hh, ww, cout, generator=g)
-    out, pl = conv(split_planes(xn, conv.cin_pad, silu=True, f16=True), res1=r1.to(dev), res2=r2.to(dev),
-                   out_f32=True, planes_ld=cout + 32, planes_silu=True)
+    xs_silu, xs = split_planes(xn, conv.cin_pad, silu=True, f16=True), split_planes(xn, conv.cin_pad, f16=True)
+    _plan_is(conv, xs_silu, "hk", planes_silu=True)
+    out, pl = conv(xs_silu, res1=r1.to(dev), res2=r2.to(dev), out_f32=True, planes_ld=cout + 32, planes_silu=True)
     sx = _q(F.silu(x.double()).float(), "f16")
     ref = F.conv2d(sx, _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1) + r1 + r2
     assert relerr(out.cpu(), ref) < 2e-5
     assert relerr(_planes_value(pl)[..., :cout].cpu(), F.silu(ref)) < 1e-3
     assert (pl.hi[..., cout:] == 0).all()
-    out2, _ = conv(split_planes(xn, conv.cin_pad, f16=True), out_f32=True)
+    _plan_is(conv, xs, "hk")
+    out2, _ = conv(xs, out_f32=True)
     ref2 = F.conv2d(_q(x, "f16"), _q(w, "f16"), b.double(), padding=1).permute(0, 2, 3, 1)
     assert relerr(out2.cpu(), ref2) < 2e-5
     if cout % 128 == 0:  # the halo2 kernel on the same operands
         monkeypatch.setenv("RF_CONV_HK", "0")
         monkeypatch.setenv("RF_CONV_HALO2", "1")
         monkeypatch.setenv("RF_CONV_HALO3", "0")
-        out3, _ = conv(split_planes(xn, conv.cin_pad, f16=True), out_f32=True)
+        _plan_is(conv, xs, "halo2", 4128)
+        out3, _ = conv(xs, out_f32=True)
         assert relerr(out3.cpu(), out2.cpu().double()) < 1e-6
 
 
@@ -1326,11 +1361,27 @@ def test_conv_group_matches_single_launches():
 @pytest.mark.parametrize("hw,halo2,hk,halo3", [(24, "0", "0", "0"), (64, "1", "0", "0"), (64, "0", "1", "0"),
                                                (64, "1", "0", "1")])
 def test_conv_border_bias(hw, halo2, hk, halo3, monkeypatch):
-    """RF_CONV_BORDER_BIAS: per-pixel bias row by border class (3 ry + rx), on the engine tile, the halo2, hk and
-    halo3 kernels (the folded output_conv1), vs torch conv + the class bias."""
-    from renderformer_amd.dpt import _Conv, split_planes
+    """RF_CONV_BORDER_BIAS: per-pixel bias row by border class (3 ry + rx) vs torch conv + the class bias.  The
+    planner, asked before the launch, showed that these cases cover the engine only: 24^2 runs the 64x64 tile, and
+    at 64^2 the 8-wave stream-K split takes the 64 tiles ahead of halo2 / hk / halo3, whatever their knobs say.
+    The cases stay, asserting that; test_conv_border_bias_halo_kernels is the same shape with RF_CONV_SK=0, on which
+    the three halo-tiled kernels (the folded output_conv1's) do run."""
     if hk == "1":
         needs_study("conv3x3_hk_kernel")
+    _border_bias(hw, halo2, hk, halo3, monkeypatch, ("ring", 64) if hw == 24 else ("ring_sk", 1288))
+
+
+@pytest.mark.parametrize("halo2,hk,halo3,want", [("1", "0", "0", ("halo2", 4128)), ("0", "1", "0", ("hk", None)),
+                                                 ("1", "0", "1", ("halo3", 0))])
+def test_conv_border_bias_halo_kernels(halo2, hk, halo3, want, monkeypatch):
+    if hk == "1":
+        needs_study("conv3x3_hk_kernel")
+    monkeypatch.setenv("RF_CONV_SK", "0")
+    _border_bias(64, halo2, hk, halo3, monkeypatch, want)
+
+
+def _border_bias(hw, halo2, hk, halo3, monkeypatch, want):
+    from renderformer_amd.dpt import _Conv, split_planes
     monkeypatch.setenv("RF_CONV_HALO2", halo2)
     monkeypatch.setenv("RF_CONV_HK", hk)
     monkeypatch.setenv("RF_CONV_HALO3", halo3)
@@ -1340,8 +1391,9 @@ def test_conv_border_bias(hw, halo2, hk, halo3, monkeypatch):
     b9 = torch.randn(9, cout, generator=g)
     x = torch.randn(2, cin, hw, hw, generator=g)
     conv = _Conv(w, None, dev, f16=True)
-    _, pl = conv(split_planes(x.permute(0, 2, 3, 1).contiguous().to(dev), conv.cin_pad, f16=True), planes_ld=cout,
-                 border_bias=b9.to(dev).contiguous())
+    xs = split_planes(x.permute(0, 2, 3, 1).contiguous().to(dev), conv.cin_pad, f16=True)
+    _plan_is(conv, xs, *want, planes_ld=cout, border_bias=b9.to(dev).contiguous())
+    _, pl = conv(xs, planes_ld=cout, border_bias=b9.to(dev).contiguous())
     ref = F.conv2d(_q(x, "f16"), _q(w, "f16"), None, padding=1)
     ry = torch.ones(hw, dtype=torch.long)
     ry[0], ry[-1] = 0, 2
@@ -1354,12 +1406,26 @@ def test_conv_border_bias(hw, halo2, hk, halo3, monkeypatch):
 
 @pytest.mark.parametrize("prec,hw", [("bf16x3", 24), ("f16", 24), ("f16h2", 32), ("f16h2", 64)])
 def test_conv_final_head(prec, hw, monkeypatch):
-    """output_conv2 + its fused head (SiLU, 1x1 32 -> 3, ELU, 10^x - 1); f16h2: on the 16 x 32-pixel halo kernel's
-    64-channel block (RF_CONV_HALO2=1; the default for 512^2 frames)."""
-    from renderformer_amd.dpt import LOG_DECODE, NCHW_OUT, _Conv, split_planes
+    """output_conv2 + its fused head (SiLU, 1x1 32 -> 3, ELU, 10^x - 1) on the engine (24^2) and, f16h2 (whole 16 x 32
+    tiles), on conv3x3_c32_kernel, which takes these shapes ahead of halo2 since it exists (so the planner says,
+    asked before the launch; RF_CONV_HALO2=1 no longer matters).  halo2's 64-channel block with the head:
+    test_conv_final_head_halo2."""
+    want = {("bf16x3", 24): ("ring_sk", 128), ("f16", 24): ("ring", 25664)}.get((prec, hw), ("c32", 0))
     if prec == "f16h2":
         monkeypatch.setenv("RF_CONV_HALO2", "1")
-        prec = "f16"
+    _final_head(prec.replace("h2", ""), hw, want)
+
+
+@pytest.mark.parametrize("hw", [32, 64])
+def test_conv_final_head_halo2(hw, monkeypatch):
+    """The fused head on halo2_kernel's 64-channel block (RF_CONV_HALO2=1 with conv3x3_c32_kernel off)."""
+    monkeypatch.setenv("RF_CONV_HALO2", "1")
+    monkeypatch.setenv("RF_CONV_C32", "0")
+    _final_head("f16", hw, ("halo2", 4064))
+
+
+def _final_head(prec, hw, want):
+    from renderformer_amd.dpt import LOG_DECODE, NCHW_OUT, _Conv, split_planes
     f16 = prec == "f16"
     g = torch.Generator(device="cpu").manual_seed(9)
     w = torch.randn(32, 64, 3, 3, generator=g) / 24
@@ -1372,6 +1438,7 @@ def test_conv_final_head(prec, hw, monkeypatch):
     y = F.elu(y, 1e-3)
     xs = split_planes(x.permute(0, 2, 3, 1).contiguous().to(dev), conv.cin_pad, f16=f16)
     fin = (wf.reshape(3, 32).to(dev), bf.to(dev), 1e-3)
+    _plan_is(conv, xs, *want, final=fin, final_flags=LOG_DECODE)
     out = conv(xs, final=fin, final_flags=LOG_DECODE)
     assert relerr(out.cpu(), (10 ** y - 1).permute(0, 2, 3, 1)) < 2e-5
     out2 = conv(xs, final=fin, final_flags=NCHW_OUT)
@@ -1393,14 +1460,32 @@ def test_split_planes_f16_rounding():
 @pytest.mark.parametrize("final", [False, True])
 def test_conv_stream_k_matches_data_parallel(monkeypatch, final, prec):
     """Few output tiles (the DPT's 32x32 / 64x64 levels): the stream-K split (8 blocks per tile here) must
-    agree with the one-block-per-tile launch and with fp64, including residuals, planes and the fused head."""
+    agree with the one-block-per-tile launch and with fp64, including residuals, planes and the fused head.
+    The planner is asked before each launch.  It showed that only the bf16x3 cases compare stream-K with
+    data-parallel: with fp16 operands conv3x3_hs_kernel (and, with the head, conv3x3_c32_kernel) takes these shapes
+    whatever RF_CONV_SK says.  Those cases stay, asserting what they run; test_conv_stream_k_f16_engine is the nearest
+    fp16 shape that does split (a fused-head bank of 64 filters never does: stream-K needs N % 128 == 0)."""
+    _stream_k_vs_data_parallel(monkeypatch, final, prec, 2)
+
+
+def test_conv_stream_k_f16_engine(monkeypatch):
+    """The same comparison where fp16 operands do reach the engine's stream-K: 5 images (5,120 pixels, above the
+    small-level tiles' 4,096) with conv3x3_hs_kernel off."""
+    monkeypatch.setenv("RF_CONV_HALO_SMALL", "0")
+    _stream_k_vs_data_parallel(monkeypatch, False, "f16", 5)
+
+
+def _stream_k_vs_data_parallel(monkeypatch, final, prec, n_img):
     from renderformer_amd.dpt import LOG_DECODE, _Conv, split_planes
     g = torch.Generator(device="cpu").manual_seed(77)
     cin = cout = 256 if not final else 64
     w = torch.randn(cout if not final else 32, cin, 3, 3, generator=g) / math.sqrt(cin * 9)
     b = torch.randn(w.shape[0], generator=g)
-    x = torch.randn(2, cin, 32, 32, generator=g)
+    x = torch.randn(n_img, cin, 32, 32, generator=g)
     f16 = prec == "f16"
+    want = {"1": ("ring_sk", 1288 if f16 else 128), "0": ("ring", 1288 if f16 else 128)}
+    if f16 and n_img == 2:
+        want = dict.fromkeys("10", ("c32", 0) if final else ("hs", 81632))
     conv = _Conv(w, b, dev, f16=f16)
     xs = split_planes(x.permute(0, 2, 3, 1).contiguous().to(dev), conv.cin_pad, silu=True, f16=f16)
     outs = []
@@ -1408,9 +1493,11 @@ def test_conv_stream_k_matches_data_parallel(monkeypatch, final, prec):
     for sk in ("1", "0"):
         monkeypatch.setenv("RF_CONV_SK", sk)
         if final:
+            _plan_is(conv, xs, *want[sk], final=fin, final_flags=LOG_DECODE)
             outs.append((conv(xs, final=fin, final_flags=LOG_DECODE), None))
         else:
-            r1 = torch.ones(2, 32, 32, cout, device=dev)
+            _plan_is(conv, xs, *want[sk], planes_silu=True)
+            r1 = torch.ones(n_img, 32, 32, cout, device=dev)
             outs.append(conv(xs, res1=r1, out_f32=True, planes_ld=cout, planes_silu=True))
     (a, pa), (bb, pb) = outs
     assert relerr(a, bb) < 1e-6
@@ -1606,8 +1693,10 @@ def test_conv_c32_final_head(cin, cout, hh, ww, n_img, n_fin, flags, monkeypatch
     xs = split_planes(x.to(dev), conv.cin_pad, f16=True)
     fl = (LOG_DECODE if flags == "log" else NCHW_OUT)
     fin = (wf.to(dev).contiguous(), bf.to(dev).contiguous(), 1e-3)
+    _plan_is(conv, xs, "c32", final=fin, final_flags=fl)
     got = conv(xs, final=fin, final_flags=fl)
     monkeypatch.setenv("RF_CONV_C32", "0")
+    _plan_is(conv, xs, "ring", 25664, final=fin, final_flags=fl)  # (the engine's 256x64 tile: < 256 halo2 blocks)
     old = _Conv(w, b, dev, f16=True)(xs, final=fin, final_flags=fl)
     xr = x.half().double().permute(0, 3, 1, 2)
     y = F.conv2d(xr, w.half().double(), b.double(), padding=1)

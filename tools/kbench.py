@@ -216,10 +216,16 @@ def conv():
                     os.environ.pop("RF_CONV_HALO_SMALL", None)
                 if not t.startswith("auto") and not t.startswith("h2") and t != "hk" and not t.startswith("h3") and not t.startswith("hs"):
                     os.environ["RF_CONV_TILE"] = t.replace("ph", "")
+                pl = conv.plan(x)  # what the label actually runs (rf_conv_plan_query), under the knobs just set
+                if pl.refuse:
+                    print(f"conv{ks}x{ks} {'f16 ' if f16 else 'bf16x3'} {cin}->{cout} @{hw} tile={t}: {pl!r} needs the "
+                          "study build (RF_LIB)")
+                    os.environ.pop("RF_CONV_TILE", None)
+                    continue
                 ms = timeit(lambda: conv(x, out_f32=True), reps=10)
                 os.environ.pop("RF_CONV_TILE", None)
                 print(f"conv{ks}x{ks} {'f16 ' if f16 else 'bf16x3'} {cin}->{cout} @{hw} tile={t}: "
-                      f"{ms*1e3:8.1f} us  {fl/ms/1e9:7.1f} TF(algorithmic)  {mf*fl/ms/1e9:7.1f} TF(MFMA issued)")
+                      f"{ms*1e3:8.1f} us  {fl/ms/1e9:7.1f} TF(algorithmic)  {mf*fl/ms/1e9:7.1f} TF(MFMA issued)  {pl!r}")
             if f16 and os.environ.get("KB_CONV_GEMM"):  # the same M, N, K as a plain bf16 GEMM (no gather)
                 a = torch.randn(hw * hw, 9 * cin, device=dev).bfloat16()
                 w = torch.randn(cout, 9 * cin, device=dev).bfloat16()
