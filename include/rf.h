@@ -465,6 +465,10 @@ int rf_frame_window(const float* frames, float* out, int n, int h, int w, int c,
  * accumulation.  Epilogue: v = conv + bias + res1 + res2 (f32 NHWC, channel stride cout), then silu if
  * RF_CONV_SILU_OUT; v is stored to `out` (f32, may be NULL) and/or split into the output planes
  * p_hi/p_lo (channel stride p_ld), of silu(v) when RF_CONV_PLANE_SILU.
+ * p_ld (a multiple of 4, >= cout): a kernel writes channels [0, cout) of every output pixel's row and nothing else --
+ * the p_ld - cout padding columns are the CALLER's to zero (the next convolution reads them as zero operand
+ * channels) and no convolution, deconvolution or grouped launch stores to them, nor to any row before the first or
+ * after the last output pixel of `out` or the planes (tests/test_guard_bands_gpu.py holds every kernel to this).
  * RF_CONV_FINAL (cout <= 64): out[pixel, f] = elu(sum_c silu(v_c) * w_fin[f, c] + b_fin[f], alpha),
  * then 10^x - 1 with RF_CONV_LOG_DECODE; [n, n_fin, h, w] layout with RF_CONV_NCHW_OUT.
  * RF_CONV_BORDER_BIAS (3x3, pad 1, stride 1, images of at least 2 x 2 pixels): `bias` holds 9 rows of cout, row 3 ry + rx with ry / rx = 0 on the

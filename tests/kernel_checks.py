@@ -11,6 +11,10 @@ Three tools, all plain torch and usable on any device:
 plus builders of inputs on which the kernels' arithmetic is exact (integer GEMM operands, attention whose weights
 are powers of two, one-hot V that names every key), and plain torch emulations of the kernels with switches that
 plant the defects the GPU tests are there to catch (tests/test_kernel_checks.py proves each one is flagged).
+
+The last section is the same for the DPT convolutions: integer and tap-mask operands (the tap mask names, per output
+element, the taps that fell inside the image), conv_bound, conv_emulation, and ConvLaunch, which calls the C entry
+points with pointers into Guarded buffers.
 """
 import math
 
@@ -316,3 +320,339 @@ def swin_attend(grid_h: int, grid_w: int, window: int, shift: int) -> torch.Tens
     for i in range(win.shape[0]):
         att[win[i][:, None], win[i][None, :]] = mask[i]
     return att
+
+
+# ------------------------------------------------------------------------------------------------ convolutions
+# Everything below serves the DPT convolution kernels (rf_conv2d_* / rf_deconv2d_* / the grouped launches): operands
+# on which the arithmetic is exact, the per-element bound for the others, a torch emulation that plants the defects
+# the GPU tests are there to catch, and a launcher that hands the C entry points pointers into Guarded buffers.
+def conv_ref(x, w, bias=None, res1=None, res2=None, stride: int = 1, pad: int = 0, deconv: int = 0) -> torch.Tensor:
+    """fp64 NHWC [n, ho, wo, cout] of x [n, cin, h, w] with w [cout, cin, kh, kw] (deconv = k: ConvTranspose2d weights
+    [cin, cout, k, k], kernel == stride == k); bias [cout] or, border-class rows, [9, cout]; residuals NHWC."""
+    x, w = x.double(), w.double()
+    b = bias.double() if bias is not None and bias.dim() == 1 else None
+    y = F.conv_transpose2d(x, w, b, stride=deconv) if deconv else F.conv2d(x, w, b, stride=stride, padding=pad)
+    y = y.permute(0, 2, 3, 1)
+    if bias is not None and bias.dim() == 2:
+        y = y + bias.double()[border_classes(y.shape[1], y.shape[2])]
+    for r in (res1, res2):
+        if r is not None:
+            y = y + r.double()
+    return y.contiguous()
+
+
+def border_classes(h: int, w: int) -> torch.Tensor:
+    """long [h, w]: the RF_CONV_BORDER_BIAS class 3 ry + rx of each pixel (rf.h: 0 first, 2 last, 1 elsewhere)."""
+    ry, rx = torch.ones(h, dtype=torch.long), torch.ones(w, dtype=torch.long)
+    ry[0], ry[-1], rx[0], rx[-1] = 0, 2, 0, 2
+    return 3 * ry[:, None] + rx[None, :]
+
+
+def int_conv_operands(n: int, cin: int, cout: int, kh: int, kw: int, h: int, w: int, seed: int = 0, amax: int = 3,
+                      bmax: int = 8, stride: int = 1, pad: int = 0, deconv: int = 0):
+    """Integer-valued x [n, cin, h, w], W ([cout, cin, kh, kw]; deconv = k: [cin, cout, k, k]) in [-amax, amax], an
+    integer bias [cout] and two integer residuals NHWC of the output's shape in [-bmax, bmax].  Every partial sum is an
+    integer below amax^2 kh kw cin + 3 bmax < 2^24, so fp32 holds it exactly in any order and over any stream-K split:
+    with fp16 operands, and with bf16x3 ones, whose lo planes are then zero."""
+    assert amax * amax * kh * kw * cin + 3 * bmax < 2 ** 24 and amax <= 256
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    x = torch.randint(-amax, amax + 1, (n, cin, h, w), generator=g).float()
+    if deconv:
+        wt = torch.randint(-amax, amax + 1, (cin, cout, deconv, deconv), generator=g).float()
+        ho, wo = h * deconv, w * deconv
+    else:
+        wt = torch.randint(-amax, amax + 1, (cout, cin, kh, kw), generator=g).float()
+        ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    bias = torch.randint(-bmax, bmax + 1, (cout,), generator=g).float()
+    res1 = torch.randint(-bmax, bmax + 1, (n, ho, wo, cout), generator=g).float()
+    res2 = torch.randint(-bmax, bmax + 1, (n, ho, wo, cout), generator=g).float()
+    return x, wt, bias, res1, res2
+
+
+def exact_planes(ref: torch.Tensor, f16: bool):
+    """The planes of an exact value: rounded once.  fp16: (fp16(v), None); bf16x3: hi = bf16(v), lo = bf16(v - hi)."""
+    if f16:
+        return ref.to(torch.float16), None
+    hi = ref.to(torch.bfloat16)
+    return hi, (ref - hi.double()).to(torch.bfloat16)
+
+
+def tap_mask_operands(n: int, cin: int, cout: int, kh: int, kw: int, h: int, w: int, deconv: int = 0):
+    """x = 1 in every channel; W[co, co % cin, ty, tx] = 2^(kw ty + tx), 0 elsewhere; no bias.  Each output element is
+    then the bit mask of the taps that fell inside its image (3x3 pad 1: 511 inside, the 8 border patterns on the
+    border).  A deconvolution (W[co % cin, co, dy, dx] = 2^(k dy + dx)) names the position in the k x k block it
+    scatters to.  b9: the integer border-class rows 1024 (class + 1) for RF_CONV_BORDER_BIAS."""
+    x = torch.ones(n, cin, h, w)
+    co = torch.arange(cout)
+    if deconv:
+        wt = torch.zeros(cin, cout, deconv, deconv)
+        wt[co % cin, co] = (2.0 ** torch.arange(deconv * deconv)).view(deconv, deconv)
+    else:
+        wt = torch.zeros(cout, cin, kh, kw)
+        wt[co, co % cin] = (2.0 ** torch.arange(kh * kw)).view(kh, kw)
+    b9 = (1024.0 * (torch.arange(9) + 1))[:, None].expand(9, cout).contiguous()
+    return x, wt, b9
+
+
+def decode_tap_mask(expected: float, observed: float, kh: int, kw: int, border: bool = False) -> str:
+    """What an observed tap-mask element says against the expected one, in words."""
+    if not (math.isfinite(observed) and observed == int(observed)):
+        return f"value {observed!r} is no integer (expected mask {int(expected)})"
+    e, o, parts = int(expected), int(observed), []
+    if border:
+        ce, co_ = e // 1024 - 1, (o - o % 1024) // 1024 - 1
+        if ce != co_:
+            parts.append(f"border class {co_} instead of {ce}")
+        e, o = e % 1024, o % 1024
+    d = o - e
+    if d and abs(d) & (abs(d) - 1) == 0 and abs(d) < 2 ** (kh * kw):  # one tap once too often / too seldom
+        t = abs(d).bit_length() - 1
+        had = (e >> t) & 1
+        parts.append(f"tap ({t // kw}, {t % kw}) counted {had + (1 if d > 0 else -1)} times, expected {had}")
+    elif d:
+        for t in range(kh * kw):
+            if (e >> t) & 1 != (o >> t) & 1:
+                parts.append(f"tap ({t // kw}, {t % kw}) " + ("missing" if (e >> t) & 1 else "counted from the padding"))
+        if o >> (kh * kw):
+            parts.append(f"sum {o} beyond the full mask {2 ** (kh * kw) - 1}")
+    return "; ".join(parts) or "equal"
+
+
+def assert_tap_mask(out: torch.Tensor, ref: torch.Tensor, kh: int, kw: int, border: bool = False, what: str = ""):
+    """out == ref bit for bit ([n, ho, wo, cout]); the first offender decoded."""
+    o, r = out.detach().double().cpu(), ref.detach().double().cpu()
+    assert o.shape == r.shape, (what, tuple(o.shape), tuple(r.shape))
+    bad = ~(o == r)
+    cnt = int(bad.sum())
+    if cnt:
+        i, y, x, f = (int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {cnt} of {r.numel()} elements differ; image {i}, pixel ({y}, {x}), filter {f}: "
+                             + decode_tap_mask(float(r[i, y, x, f]), float(o[i, y, x, f]), kh, kw, border))
+
+
+def conv_bound(x, w, bias, res1, res2, k_terms: int, out_dtype: torch.dtype, silu: bool = False, stride: int = 1,
+               pad: int = 0, deconv: int = 0, ref: torch.Tensor = None, operand_rel: float = 0.0) -> torch.Tensor:
+    """Per-element bound on |out - ref| for v = conv(x, w) + bias + res1 + res2 accumulated in fp32 in any order and
+    written as out_dtype (of silu(v) with `silu`).  acc_bound's argument: each of the k_terms - 1 adds of the dot
+    product and the three epilogue adds perturbs a partial sum by at most one fp32 ulp, and every partial sum is at
+    most mag = |x| * |w| + |bias| + |res1| + |res2|: e = (k_terms + 3) 2^-23 mag, the products being exact.
+    operand_rel: what the products themselves omit, relative to |x| * |w| (bf16x3 leaves out lo * lo: 2^-16).
+    silu: swiglu_bound's silu step, 1.1 e + 2^-20 |silu(ref)| (|silu'| <= 1.1; the fast exponential and reciprocal
+    within 8 fp32 ulps).  Then out_rounding."""
+    prod = conv_ref(x.abs(), w.abs(), None, None, None, stride, pad, deconv)
+    mag = conv_ref(x.abs(), w.abs(), None if bias is None else bias.abs(), None if res1 is None else res1.abs(),
+                   None if res2 is None else res2.abs(), stride, pad, deconv)
+    e = (k_terms + 3) * F32_ULP * mag + operand_rel * prod
+    if ref is None:
+        ref = conv_ref(x, w, bias, res1, res2, stride, pad, deconv)
+    if silu:
+        ref = F.silu(ref)
+        e = 1.1 * e + 2.0 ** -20 * ref.abs()
+    return e + out_rounding(ref.abs(), e, out_dtype)
+
+
+def conv_emulation(x, w, bias=None, res1=None, res2=None, pad: int = 1, drop_chunk=None, halo_col_zero=None,
+                   prev_image_row=None, wrong_class=None, chunk: int = 32) -> torch.Tensor:
+    """A stride-1 convolution as the kernels compute it, in fp32 (NHWC out), with planted defects:
+      drop_chunk = (img, y, x, tap, c)   one `chunk`-channel slice c of tap (ty, tx) = divmod(tap, kw) is missing at
+                                         one pixel, for every filter;
+      halo_col_zero = x0                 the tile whose first column is x0 reads its left halo column (x0 - 1) as zero;
+      prev_image_row = img               image img reads its row -1 from the last row of image img - 1 (adjacent in
+                                         memory) instead of the zero row;
+      wrong_class = (corner y, corner x, cls)   RF_CONV_BORDER_BIAS (bias [9, cout]): that pixel of every image takes
+                                         the bias row of class cls."""
+    x, w = x.float(), w.float()
+    n, cin, h, wd = x.shape
+    kh, kw = w.shape[2], w.shape[3]
+    y = F.conv2d(x, w, None, padding=pad).permute(0, 2, 3, 1).contiguous()
+    xp = F.pad(x, (pad, pad, pad, pad))
+    if drop_chunk is not None:
+        i, py, px, tap, c = drop_chunk
+        ty, tx = divmod(tap, kw)
+        sl = slice(c * chunk, (c + 1) * chunk)
+        y[i, py, px] -= w[:, sl, ty, tx] @ xp[i, sl, py + ty, px + tx]
+    if halo_col_zero is not None:
+        x0 = halo_col_zero
+        assert pad == 1 and 0 < x0 < wd
+        for ty in range(kh):  # tap column 0 of output column x0 reads input column x0 - 1
+            y[:, :, x0] -= torch.einsum("nch,oc->nho", xp[:, :, ty:ty + h, x0], w[:, :, ty, 0])
+    if prev_image_row is not None:
+        i = prev_image_row
+        assert pad == 1 and 0 < i < n
+        last = F.pad(x[i - 1, :, h - 1], (1, 1))  # [cin, w + 2]
+        for tx in range(kw):
+            y[i, 0] += last[:, tx:tx + wd].t() @ w[:, :, 0, tx].t()
+    if bias is not None and bias.dim() == 2:
+        cls = border_classes(h, wd)
+        if wrong_class is not None:
+            cls[wrong_class[0], wrong_class[1]] = wrong_class[2]
+        y = y + bias.float()[cls]
+    elif bias is not None:
+        y = y + bias.float()
+    for r in (res1, res2):
+        if r is not None:
+            y = y + r.float()
+    return y
+
+
+def emulated_store(g: "Guarded", values: torch.Tensor, past_cout: bool = False) -> "Guarded":
+    """Write `values` ([rows, cols]) into a Guarded output as a kernel's epilogue would.  past_cout plants a 4-element
+    store one channel group past the last real channel in the LAST row (rows before it would be overwritten by their
+    successors in a dense buffer): zeros, the value a padded accumulator column holds -- which an `== 0` check of
+    caller-zeroed padding columns cannot see."""
+    g.fill(values)
+    if past_cout:
+        flat = g.buf.view(-1)
+        at = (g.g + g.rows - 1) * g.ld + g.col_off + g.cols
+        flat[at:at + 4] = 0
+    return g
+
+
+def _gptr(g_) -> int:
+    return 0 if g_ is None else g_.view.data_ptr()
+
+
+class ConvLaunch:
+    """One convolution / deconvolution call through the C entry points (rf_conv2d_f16, rf_conv2d_bf16x3, rf_deconv2d_*)
+    with every device buffer but the weights inside a Guarded allocation.  `conv` (dpt._Conv) supplies the weight
+    layout and the plan.
+
+    Inputs (NaN surround): the operand planes [pixels, cin_pad] (padded channels zero, as rf.h requires; the guard
+    rows are what a kernel reads as row -1 of image 0 or row h of the last image if it does not take the zero row),
+    the residuals [pixels, cout], the bias [1 | 9, cout].  Outputs (OUT_GUARD = 256 guard rows, the tallest tile, so an
+    overrun of a tile's height lands inside the allocation and is reported): `out` dense [pixels, cout] (the head:
+    [pixels, n_fin] or, NCHW, [n n_fin, ho wo]) and the planes [pixels, cout] inside rows of ld > cout starting
+    col_off columns in."""
+    OUT_GUARD = 256
+
+    def __init__(self, conv, x: torch.Tensor, x_lo: torch.Tensor = None, stride: int = 1, pad: int = None,
+                 bias: torch.Tensor = None, res1=None, res2=None, device="cuda"):
+        self.conv, self.dev = conv, device
+        n, cin, h, w = x.shape
+        assert cin == conv.cin
+        self.n, self.h, self.w, self.stride = n, h, w, stride
+        self.pad = conv.kh // 2 if pad is None else pad
+        if conv.k:
+            self.ho, self.wo = h * conv.k, w * conv.k
+        else:
+            self.ho = (h + 2 * self.pad - conv.kh) // stride + 1
+            self.wo = (w + 2 * self.pad - conv.kw) // stride + 1
+        self.pix = n * self.ho * self.wo
+        dt = torch.float16 if conv.f16 else torch.bfloat16
+        gin = 2 * (w + 2)  # more than one image row and its two halo pixels before and after the images
+
+        def plane(v):
+            rows = torch.zeros(n * h * w, conv.cin_pad)
+            rows[:, :cin] = v.permute(0, 2, 3, 1).reshape(-1, cin)
+            assert torch.equal(rows.to(dt).float(), rows), "operand planes must hold values exact in their type"
+            return Guarded(n * h * w, conv.cin_pad, dt, device, g=gin, ld=conv.cin_pad).fill(rows)
+
+        self.x_hi = plane(x)
+        self.x_lo = None if conv.f16 else plane(torch.zeros_like(x) if x_lo is None else x_lo)
+        self.bias = None if bias is None else Guarded(bias.numel() // conv.cout, conv.cout, torch.float32, device,
+                                                      ld=conv.cout).fill(bias.view(-1, conv.cout))
+        self.res = [None if r is None else Guarded(self.pix, conv.cout, torch.float32, device, g=4, ld=conv.cout)
+                    .fill(r.reshape(self.pix, conv.cout)) for r in (res1, res2)]
+        self.out = self.p_hi = self.p_lo = None
+
+    def plan(self, flags: int = 0, n_fin: int = 0):
+        from renderformer_amd import _lib
+        c = self.conv
+        return _lib.conv_plan(c.f16, self.n, self.h, self.w, c.cin_pad, c.cout, c.cout_pad, c.kh, c.kw, self.stride,
+                              self.pad, flags, n_fin, c.k, int(_lib.load(require_device=False).rf_gemm_workspace_bytes()))
+
+    def alloc(self, want_out: bool = True, plane_ld: int = None, col_off: int = 0, flags: int = 0, final=None) -> int:
+        """Fresh Guarded outputs for one launch (and the head's operands); returns the flags to pass."""
+        c, dev, G = self.conv, self.dev, self.OUT_GUARD
+        self.out = self.p_hi = self.p_lo = self.w_fin = self.b_fin = None
+        self.plane_ld, self.n_fin, self.alpha = plane_ld or 0, 0, 0.0
+        if final is not None:
+            self.n_fin, self.alpha = final[0].shape[0], final[2]
+            self.w_fin = Guarded(self.n_fin, c.cout, torch.float32, dev, ld=c.cout).fill(final[0])
+            self.b_fin = Guarded(1, self.n_fin, torch.float32, dev, ld=self.n_fin).fill(final[1][None])
+            flags |= 4
+            hw = self.ho * self.wo
+            self.out = (Guarded(self.n * self.n_fin, hw, torch.float32, dev, g=G, ld=hw) if flags & 16 else
+                        Guarded(self.pix, self.n_fin, torch.float32, dev, g=G, ld=self.n_fin))
+        elif want_out:
+            self.out = Guarded(self.pix, c.cout, torch.float32, dev, g=G, ld=c.cout)
+        if plane_ld:
+            assert col_off % 4 == 0 and plane_ld % 4 == 0 and col_off + c.cout <= plane_ld and plane_ld > c.cout
+            dt = torch.float16 if c.f16 else torch.bfloat16
+            self.p_hi = Guarded(self.pix, c.cout, dt, dev, g=G, ld=plane_ld, col_off=col_off)
+            self.p_lo = None if c.f16 else Guarded(self.pix, c.cout, dt, dev, g=G, ld=plane_ld, col_off=col_off)
+        return flags
+
+    def views(self):
+        return tuple(None if g_ is None else g_.view for g_ in (self.out, self.p_hi, self.p_lo))
+
+    def __call__(self, want_out: bool = True, plane_ld: int = None, col_off: int = 0, flags: int = 0, final=None):
+        """Launch.  final = (w_fin [n_fin, cout], b_fin [n_fin], elu_alpha): the fused head (flags gets RF_CONV_FINAL).
+        Returns (out view or None, plane hi view or None, plane lo view or None); the Guarded buffers stay on self."""
+        from renderformer_amd._lib import call, ptr, stream
+        from renderformer_amd.ops import _gemm_workspace
+        c = self.conv
+        ws = _gemm_workspace(self.x_hi.buf.device)
+        flags = self.alloc(want_out, plane_ld, col_off, flags, final)
+        p = _gptr
+        tail = (p(self.out), p(self.p_hi)) + (() if c.f16 else (p(self.p_lo),)) + (self.plane_ld,)
+        head = (p(self.x_hi),) + (() if c.f16 else (p(self.x_lo),)) + (self.n, self.h, self.w, c.cin_pad, ptr(c.w_hi)) + \
+               (() if c.f16 else (ptr(c.w_lo),))
+        if c.k:
+            assert not flags and self.res == [None, None]
+            call("rf_deconv2d_f16" if c.f16 else "rf_deconv2d_bf16x3", *head, c.cout, c.k, p(self.bias), *tail, ptr(ws),
+                 ws.numel(), stream())
+        else:
+            call("rf_conv2d_f16" if c.f16 else "rf_conv2d_bf16x3", *head, c.cout, c.cout_pad, c.kh, c.kw, self.stride,
+                 self.pad, p(self.bias), p(self.res[0]), p(self.res[1]), *tail, flags, p(self.w_fin), p(self.b_fin),
+                 self.n_fin, self.alpha, ptr(ws), ws.numel(), stream())
+        torch.cuda.synchronize()
+        return self.views()
+
+    def assert_untouched(self, what: str = ""):
+        for name, g_ in (("out", self.out), ("plane hi", self.p_hi), ("plane lo", self.p_lo)):
+            if g_ is not None:
+                g_.assert_untouched(what=f"{what} {name}")
+
+    def shaped(self, view: torch.Tensor) -> torch.Tensor:
+        """A [pixels, cout] output view as NHWC [n, ho, wo, cout] on the CPU."""
+        return view.detach().cpu().reshape(self.n, self.ho, self.wo, -1)
+
+
+def conv_group_launch(members, flags) -> None:
+    """rf_conv2d_f16_group over ConvLaunch members whose outputs alloc() made (fp16; residuals are not part of a
+    grouped launch); flags: one per member (RF_CONV_PLANE_SILU / RF_CONV_BORDER_BIAS)."""
+    import ctypes
+    from renderformer_amd._lib import call, ptr, stream
+    from renderformer_amd.dpt import _ConvDesc
+    descs = (_ConvDesc * len(members))()
+    for d, m, fl in zip(descs, members, flags):
+        c = m.conv
+        assert c.f16 and m.res == [None, None]
+        d.in_, d.w, d.bias, d.out, d.p_out = _gptr(m.x_hi), ptr(c.w_hi), _gptr(m.bias), _gptr(m.out), _gptr(m.p_hi)
+        d.n_img, d.hi, d.wi, d.cin_pad, d.cout, d.cout_pad = m.n, m.h, m.w, c.cin_pad, c.cout, c.cout_pad
+        d.kh, d.kw, d.stride, d.pad, d.deconv_k, d.p_ld, d.flags = c.kh, c.kw, m.stride, m.pad, c.k, m.plane_ld, fl
+    call("rf_conv2d_f16_group", len(members), ctypes.cast(descs, ctypes.c_void_p), stream())
+    torch.cuda.synchronize()
+
+
+def conv1x1_group_launch(members) -> None:
+    """rf_conv1x1_f16_group over ConvLaunch members (fp16 1x1 convolutions over images of one size, plane outputs)."""
+    import ctypes
+    from renderformer_amd._lib import call, ptr, stream
+    k = len(members)
+    arrs = []
+
+    def arr(ct, vals):
+        a = (ct * k)(*vals)
+        arrs.append(a)
+        return ctypes.cast(a, ctypes.c_void_p)
+
+    m0 = members[0]
+    assert all(m.conv.f16 and m.conv.kh == 1 and not m.conv.k and (m.n, m.h, m.w) == (m0.n, m0.h, m0.w) for m in members)
+    call("rf_conv1x1_f16_group", k, arr(ctypes.c_void_p, [_gptr(m.x_hi) for m in members]),
+         arr(ctypes.c_int, [m.conv.cin_pad for m in members]), arr(ctypes.c_void_p, [ptr(m.conv.w_hi) for m in members]),
+         arr(ctypes.c_int, [m.conv.cout for m in members]), arr(ctypes.c_int, [m.conv.cout_pad for m in members]),
+         arr(ctypes.c_void_p, [_gptr(m.bias) for m in members]), arr(ctypes.c_void_p, [_gptr(m.p_hi) for m in members]),
+         arr(ctypes.c_int, [m.plane_ld for m in members]), m0.n, m0.h, m0.w, stream())
+    torch.cuda.synchronize()

@@ -4,7 +4,8 @@ Every entry point whose C signature takes a leading dimension for what it writes
 (guard rows, ld above the width, a sentinel everywhere outside the view) and NaN-surrounded strided inputs, one small
 shape per vector-width path with a row count that is no multiple of the 4 rows of a block; the value check is the one
 the op's older test makes, applied to every element.  rf_embed, reached until now only through whole-frame parity, is
-compared with fp64 per element on both of its paths, which must agree bit for bit.
+compared with fp64 per element on both of its paths, which must agree bit for bit.  The last section guards every
+buffer of the DPT convolution entry points.
 """
 import math
 
@@ -12,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as cc
 import kernel_checks as kc
 from kernel_checks import Guarded
 from oracle import rf_ref
@@ -341,3 +343,97 @@ def test_embed_matches_fp64(case):
                                   _gin(in0).view if use0 else None, gw0.view[0] if use0 else None, eps,
                                   g1.view if use1 else None, gw1.view[0] if use1 else None, eps)
                         assert torch.equal(gout.view[out_rows.long().to(dev)], outs[0]), f"{tag}: vector vs scalar"
+
+
+# ------------------------------------------------------------------------------------------------ DPT convolutions
+# The M-tail, padded-bank, deconvolution, NCHW-head, multi-image and grouped cases of conv_cases.py with every device
+# buffer but the weights guarded (kernel_checks.ConvLaunch): 256 sentinel rows around `out` and the planes, sentinel
+# padding columns in the planes (rf.h: the caller zeroes them, a kernel never writes them), NaN around the operand
+# planes (the rows before image 0 and after the last image), the residuals and the bias rows.  Integer operands: the
+# outputs must be finite and bit-equal to fp64 all the same.  Each case launches twice, the allocation reset in
+# between and the planes at another column offset, so no value of the first launch can pass for the second.
+CONV_GUARDED = ["ring64-mtail", "ring64-padded-bank", "ring64-stride2", "ring25664-bank32", "tile2561-gather",
+                "tile256-gather", "sk64", "sk128", "sk1288-1x1", "hs-3img-3chunk", "hs-163264", "halo2-4128",
+                "halo2-4064", "halo3", "halo3-16chunk", "tile128-halo", "tile25664-halo", "deconv2", "deconv4",
+                "deconv2-tile256", "phased-dense", "phased-gather", "bf-sk128", "bf-ring2561", "bf-deconv4"]
+
+
+@pytest.mark.parametrize("cid", CONV_GUARDED)
+def test_conv_guarded(cid, monkeypatch):
+    case = cc.BY_ID[cid]
+    cc.set_env(case, monkeypatch)
+    L, ref = cc.exact_case(case, dev, seed=7 + len(cid))
+    cc.assert_plan(case, L)
+    for ld, col_off in ((case.cout + 8, 4), (case.cout + 40, 24)):
+        out, hi, lo = L(want_out=True, plane_ld=ld, col_off=col_off)
+        what = f"{cid} col_off {col_off}"
+        kc.assert_finite(out, what)
+        assert torch.equal(L.shaped(out).double(), ref), what
+        ehi, elo = kc.exact_planes(ref, L.conv.f16)
+        assert torch.equal(L.shaped(hi), ehi) and (elo is None or torch.equal(L.shaped(lo), elo)), what
+        L.assert_untouched(what)  # guard rows and padding columns still hold the sentinel
+        for g_ in (L.out, L.p_hi, L.p_lo):
+            if g_ is not None:
+                g_.reset()
+    out, hi, lo = L(want_out=False, plane_ld=case.cout + 8, col_off=0)  # plane-only: the fp16 frame's form
+    assert torch.equal(L.shaped(hi), kc.exact_planes(ref, L.conv.f16)[0]), cid
+    L.assert_untouched(cid + " plane-only")
+
+
+@pytest.mark.parametrize("nchw", [True, False], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("cid", ["head-c32", "head-halo2", "head-ring"])
+def test_conv_head_guarded(cid, nchw, monkeypatch):
+    """The fused head's only output, [n n_fin, h w] (NCHW) or [pixels, n_fin], inside 256 guard rows; w_fin and b_fin
+    NaN-surrounded too.  Two launches must agree bit for bit and stay finite (the values: test_conv_exact_gpu.py)."""
+    case = cc.BY_ID[cid]
+    cc.set_env(case, monkeypatch)
+    x, w, b, _, _ = kc.int_conv_operands(case.n, case.cin, case.cout, 3, 3, case.h, case.w, seed=3, amax=1, pad=1)
+    g = torch.Generator(device="cpu").manual_seed(6)
+    fin = (torch.randn(3, case.cout, generator=g) / 64, torch.randn(3, generator=g) * 0.1, 1e-3)
+    L = cc.launcher(case, x, w, b, device=dev)
+    flags = 8 | (16 if nchw else 0)
+    cc.assert_plan(case, L, 4 | flags, 3)
+    outs = []
+    for _ in range(2):
+        out, _, _ = L(flags=flags, final=fin)
+        kc.assert_finite(out, cid)
+        L.assert_untouched(cid)
+        outs.append(out.clone())
+    assert torch.equal(outs[0], outs[1])
+
+
+def test_conv_group_guarded():
+    """rf_conv2d_f16_group and rf_conv1x1_f16_group: every member's buffers guarded, launched twice with the planes at
+    another column offset."""
+    for col_off in (4, 16):
+        members = []
+        for q, (kind, cin, cout, k, stride, pad, h, w, bias, out_f32) in enumerate(cc.GROUP):
+            case = cc.Case(f"group{q}", "f16", kind, cin, cout, k, stride, pad, h, w, 2, {}, None, None, False, "")
+            dk = k if kind == "deconv" else 0
+            x, wt, b, _, _ = kc.int_conv_operands(2, cin, cout, k, k, h, w, seed=20 + q, stride=stride or 1, pad=pad,
+                                                  deconv=dk)
+            b = b if bias else None
+            L = cc.launcher(case, x, wt, b, device=dev)
+            L.alloc(want_out=out_f32, plane_ld=cout + 32, col_off=col_off)
+            members.append((L, kc.conv_ref(x, wt, b, None, None, stride or 1, pad, dk)))
+        kc.conv_group_launch([m for m, _ in members], [0] * len(members))
+        for q, (L, ref) in enumerate(members):
+            out, hi, _ = L.views()
+            what = f"group member {q} col_off {col_off}"
+            assert out is None or torch.equal(L.shaped(out).double(), ref), what
+            assert torch.equal(L.shaped(hi), ref.half()), what
+            L.assert_untouched(what)
+        h, w, n = cc.GROUP_1X1_HW
+        for which, spec in cc.GROUP_1X1.items():
+            members = []
+            for q, (cin, cout, bias) in enumerate(spec):
+                case = cc.Case(f"g1x1-{q}", "f16", "conv", cin, cout, 1, 1, 0, h, w, n, {}, None, None, False, "")
+                x, wt, b, _, _ = kc.int_conv_operands(n, cin, cout, 1, 1, h, w, seed=30 + q)
+                b = b if bias else None
+                L = cc.launcher(case, x, wt, b, device=dev)
+                L.alloc(want_out=False, plane_ld=cout + 32, col_off=col_off)
+                members.append((L, kc.conv_ref(x, wt, b)))
+            kc.conv1x1_group_launch([m for m, _ in members])
+            for q, (L, ref) in enumerate(members):
+                assert torch.equal(L.shaped(L.views()[1]), ref.half()), (which, q, col_off)
+                L.assert_untouched(f"1x1 group {which} member {q} col_off {col_off}")

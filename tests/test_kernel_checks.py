@@ -2,7 +2,11 @@
 
 The evidence that the exact-arithmetic and guard-band GPU tests can fail: every defect planted in an emulation (a lost
 K slice, a scaled row, a key counted twice or dropped, a store into a guard row or the ld padding, a load from the
-input padding) is flagged by the helper the GPU tests use, and the unmodified emulation passes every helper.
+input padding) is flagged by the helper the GPU tests use, and the unmodified emulation passes every helper.  The
+last section does the same for the convolution helpers: a dropped 32-channel chunk of one tap at one pixel, a halo
+column read as zero, a row read from the previous image, a wrong border class and a store past cout are each flagged
+by the exact form, the tap mask, conv_bound or the guard band -- and the first of them passes the whole-tensor
+`relerr < 1e-3` plane bar of the older conv tests.
 """
 import math
 
@@ -268,3 +272,157 @@ def test_swin_attend_matches_roll_partition_and_mask():
             assert int(att.sum(1).min()) == int(att.sum(1).max()) == 64
         else:
             assert int(att.sum(1).min()) < 64
+
+
+# ------------------------------------------------------------------------------------------------ convolutions
+def relerr(a, b):
+    a, b = a.double(), b.double()
+    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def test_int_conv_operands_are_exact_in_fp32():
+    """3x3, cin 512: every partial sum stays an integer below 2^24 (bound 9 * 9 * 512 + 3 * 8 = 41,496; the largest
+    |v| of this draw is about 1,100), so the fp32 convolution equals the fp64 one bit for bit, in another summation
+    order (the emulation adds the bias and residuals after the taps) too; the planes are that value rounded once."""
+    x, w, b, r1, r2 = kc.int_conv_operands(2, 512, 64, 3, 3, 8, 8, seed=1, pad=1)
+    ref = kc.conv_ref(x, w, b, r1, r2, pad=1)
+    assert 1000 < float(ref.abs().max()) < 3 * 3 * 9 * 512 + 24
+    assert torch.equal(ref, ref.round()) and ref.dtype == torch.float64
+    assert torch.equal(kc.conv_emulation(x, w, b, r1, r2).double(), ref)
+    halves = kc.conv_emulation(x[:, :256], w[:, :256]) + kc.conv_emulation(x[:, 256:], w[:, 256:], b, r1, r2)
+    assert torch.equal(halves.double(), ref)  # a two-way split of K
+    hi, lo = kc.exact_planes(ref, f16=True)
+    assert lo is None and torch.equal(hi.double(), ref)  # |v| <= 2,048: fp16 holds these integers exactly
+    big = ref * 37.0  # up to about 41,000: fp16 rounds (spacing 32), bf16 hi + lo holds 16 bits
+    hi, lo = kc.exact_planes(big, f16=False)
+    assert not torch.equal(hi.double(), big) and float((hi.double() + lo.double() - big).abs().max()) <= 2 ** -16 * 41496
+    with pytest.raises(AssertionError):
+        kc.int_conv_operands(1, 2048, 4, 3, 3, 4, 4, amax=32)  # 1,024 * 9 * 2,048 > 2^24
+    xd, wd, bd, _, _ = kc.int_conv_operands(2, 64, 16, 1, 1, 3, 5, seed=2, deconv=4)
+    rd = kc.conv_ref(xd, wd, bd, deconv=4)
+    assert rd.shape == (2, 12, 20, 16) and torch.equal(rd, rd.round())
+
+
+def test_tap_mask_names_the_taps():
+    x, w, b9 = kc.tap_mask_operands(2, 32, 64, 3, 3, 4, 5)
+    m = kc.conv_ref(x, w, None, pad=1)
+    assert (m[:, 1:-1, 1:-1] == 511).all()
+    # corners and edges: the taps that read the zero border are missing (tap t = 3 ty + tx has the value 2^t)
+    assert [int(m[1, y, x_, 33]) for y, x_ in ((0, 0), (0, 2), (0, 4), (2, 0), (3, 0), (3, 4))] == \
+        [432, 504, 216, 438, 54, 27]
+    mb = kc.conv_ref(x, w, b9, pad=1)
+    assert torch.equal(mb - m, (1024.0 * (kc.border_classes(4, 5) + 1))[None, :, :, None].expand_as(m).double())
+    xd, wd, _ = kc.tap_mask_operands(1, 32, 64, 1, 1, 2, 3, deconv=2)
+    md = kc.conv_ref(xd, wd, None, deconv=2)
+    assert torch.equal(md[0, :, :, 40], torch.tensor([[1., 2.] * 3, [4., 8.] * 3] * 2, dtype=torch.float64))
+    assert kc.decode_tap_mask(511, 513, 3, 3) == "tap (0, 1) counted 2 times, expected 1"
+    assert kc.decode_tap_mask(511, 447, 3, 3) == "tap (2, 0) counted 0 times, expected 1"
+    assert kc.decode_tap_mask(432, 438, 3, 3) == \
+        "tap (0, 1) counted from the padding; tap (0, 2) counted from the padding"
+    assert kc.decode_tap_mask(1024 * 5 + 511, 1024 * 4 + 511, 3, 3, border=True) == "border class 3 instead of 4"
+    kc.assert_tap_mask(m.float(), m, 3, 3)
+    bad = m.clone()
+    bad[1, 0, 4, 96 % 64] += 2.0
+    with pytest.raises(AssertionError, match=r"image 1, pixel \(0, 4\), filter 32: tap \(0, 1\) counted 1 times, expected 0"):
+        kc.assert_tap_mask(bad, m, 3, 3, what="planted")
+
+
+DEFECTS = ["dropped_chunk", "halo_column_zero", "previous_image_row", "wrong_border_class", "store_past_cout"]
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_conv_planted_defect_is_flagged(defect):
+    """Each defect of conv_emulation against the assertion the GPU tests make: the exact form (torch.equal with the
+    fp64 reference), the tap mask with its decoded message, and the guard band."""
+    n, cin, cout, h, w = 2, 64, 32, 6, 16
+    x, wt, b, r1, r2 = kc.int_conv_operands(n, cin, cout, 3, 3, h, w, seed=3, pad=1)
+    ref = kc.conv_ref(x, wt, b, r1, r2, pad=1)
+    assert torch.equal(kc.conv_emulation(x, wt, b, r1, r2).double(), ref)
+    xm, wm, b9 = kc.tap_mask_operands(n, cin, cout, 3, 3, h, w)
+    mask = kc.conv_ref(xm, wm, None, pad=1)
+    kc.assert_tap_mask(kc.conv_emulation(xm, wm), mask, 3, 3)
+    if defect == "dropped_chunk":
+        assert not torch.equal(kc.conv_emulation(x, wt, b, r1, r2, drop_chunk=(1, 2, 7, 5, 1)).double(), ref)
+        with pytest.raises(AssertionError, match=r"image 1, pixel \(2, 7\), filter 32: tap \(1, 2\) counted 0 times"):
+            # (filters 32 .. 63 read channels 32 .. 63, chunk 1)
+            xm2, wm2, _ = kc.tap_mask_operands(n, cin, 64, 3, 3, h, w)
+            kc.assert_tap_mask(kc.conv_emulation(xm2, wm2, drop_chunk=(1, 2, 7, 5, 1)),
+                               kc.conv_ref(xm2, wm2, None, pad=1), 3, 3)
+    elif defect == "halo_column_zero":
+        assert not torch.equal(kc.conv_emulation(x, wt, b, r1, r2, halo_col_zero=8).double(), ref)
+        with pytest.raises(AssertionError, match=r"image 0, pixel \(0, 8\), filter 0: tap \(1, 0\) missing; tap \(2, 0\) "
+                                                 r"missing"):
+            kc.assert_tap_mask(kc.conv_emulation(xm, wm, halo_col_zero=8), mask, 3, 3)
+    elif defect == "previous_image_row":
+        assert not torch.equal(kc.conv_emulation(x, wt, b, r1, r2, prev_image_row=1).double(), ref)
+        with pytest.raises(AssertionError, match=r"image 1, pixel \(0, 0\), filter 0: tap \(0, 1\) counted from the "
+                                                 r"padding; tap \(0, 2\) counted from the padding"):
+            kc.assert_tap_mask(kc.conv_emulation(xm, wm, prev_image_row=1), mask, 3, 3)
+    elif defect == "wrong_border_class":
+        maskb = kc.conv_ref(xm, wm, b9, pad=1)
+        kc.assert_tap_mask(kc.conv_emulation(xm, wm, b9), maskb, 3, 3, border=True)
+        with pytest.raises(AssertionError, match=r"image 0, pixel \(5, 15\), filter 0: border class 7 instead of 8"):
+            kc.assert_tap_mask(kc.conv_emulation(xm, wm, b9, wrong_class=(5, 15, 7)), maskb, 3, 3, border=True)
+    else:
+        vals = ref.reshape(-1, cout)
+        for g_ in (kc.Guarded(vals.shape[0], cout, torch.float32, g=256, ld=cout),            # dense out: guard rows
+                   kc.Guarded(vals.shape[0], cout, torch.float16, g=256, ld=cout + 8, col_off=4)):  # planes: ld padding
+            kc.emulated_store(g_, vals).assert_untouched()
+            assert torch.equal(g_.view.double(), vals)
+            with pytest.raises(AssertionError, match=rf"first at \(row {vals.shape[0] if g_.ld == cout else vals.shape[0] - 1}"
+                                                     rf", col {0 if g_.ld == cout else cout}\)"):
+                kc.emulated_store(g_.reset(), vals, past_cout=True).assert_untouched(what=defect)
+        # what the suite had: padding columns the caller zeroed compared with zero -- the stray store of zeros passes
+        pl = torch.zeros(vals.shape[0], cout + 8, dtype=torch.float16)
+        pl[:, :cout] = vals.half()
+        pl[-1, cout:cout + 4] = 0
+        assert (pl[:, cout:] == 0).all()
+
+
+@pytest.mark.parametrize("cin,cout,hh,ww,n_img,score", [(256, 256, 64, 64, 1, 6.03e-4), (256, 128, 32, 64, 2, 8.09e-4)])
+def test_one_pixel_defect_passes_the_plane_bar_and_fails_the_bound(cin, cout, hh, ww, n_img, score):
+    """test_conv_halo2's operands at two of its shapes (randn weights / sqrt(9 cin), bias, two residuals, SiLU fp16
+    planes), one 32-channel chunk of the centre tap missing at the centre pixel of the last image, for every filter.
+    Measured whole-tensor relative L2 of the SiLU planes against fp64:
+        (256, 256, 64, 64, 1): 6.03e-4 with the defect, 2.08e-4 without (fp16 rounding alone); fp32 out 5.4e-4
+        (256, 128, 32, 64, 2): 8.09e-4 with the defect, 2.08e-4 without;                       fp32 out 6.9e-4
+    (other pixels score 6e-4 to 1.0e-3): the defect passes the suite's `relerr < 1e-3` plane bar -- and fails
+    assert_elementwise with conv_bound at about 200 / 80 elements, all of that pixel, while the clean emulation stays
+    within 0.4 of the bound."""
+    import torch.nn.functional as F
+    g = torch.Generator(device="cpu").manual_seed(cin * hh + cout + ww)
+    w = torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9)
+    b = torch.randn(cout, generator=g)
+    x = torch.randn(n_img, cin, hh, ww, generator=g)
+    r1 = torch.randn(n_img, hh, ww, cout, generator=g)
+    r2 = torch.randn(n_img, hh, ww, cout, generator=g)
+    sx, wq = F.silu(x.double()).float().half().double(), w.half().double()  # the operands as the kernel sees them
+    ref = kc.conv_ref(sx, wq, b, r1, r2, pad=1)
+    pixel = (n_img - 1, hh // 2, ww // 2)
+    bad = F.silu(kc.conv_emulation(sx, wq, b, r1, r2, drop_chunk=(*pixel, 4, 3))).half()
+    good = F.silu(kc.conv_emulation(sx, wq, b, r1, r2)).half()
+    e_bad, e_good = relerr(bad, F.silu(ref)), relerr(good, F.silu(ref))
+    print(f"planes relerr: planted defect {e_bad:.3e}, clean {e_good:.3e}")
+    assert e_good < 2.2e-4 and abs(e_bad - score) < 0.02 * score and e_bad < 1e-3  # the old bar passes the defect
+    bound = kc.conv_bound(sx, wq, b, r1, r2, 9 * cin, torch.float16, silu=True, pad=1, ref=ref)
+    assert kc.assert_elementwise(good, F.silu(ref), bound, "clean") < 0.5
+    with pytest.raises(AssertionError, match=rf"worst at \({pixel[0]}, {pixel[1]}, {pixel[2]}, "):
+        kc.assert_elementwise(bad, F.silu(ref), bound, "planted")
+
+
+def test_conv_bound_terms():
+    """conv_bound on a case small enough to check by hand: one pixel, one tap, two channels."""
+    x = torch.tensor([1.0, -2.0]).view(1, 2, 1, 1)
+    w = torch.tensor([0.5, 0.25]).view(1, 2, 1, 1)
+    b, r1 = torch.tensor([-1.0]), torch.full((1, 1, 1, 1), 3.0)
+    mag = 0.5 + 0.5 + 1.0 + 3.0  # |x| |w| + |bias| + |res1|; ref = 0.5 - 0.5 - 1 + 3 = 2
+    e = (2 + 3) * 2.0 ** -23 * mag
+    assert float(kc.conv_bound(x, w, b, r1, None, 2, torch.float32)) == pytest.approx(e, rel=1e-12)
+    assert float(kc.conv_bound(x, w, b, r1, None, 2, torch.float16)) == \
+        pytest.approx(e + 2.0 ** -11 * (2.0 + e) + 2.0 ** -25, rel=1e-12)
+    s = 2.0 / (1.0 + math.exp(-2.0))
+    es = 1.1 * e + 2.0 ** -20 * s
+    assert float(kc.conv_bound(x, w, b, r1, None, 2, torch.float16, silu=True)) == \
+        pytest.approx(es + 2.0 ** -11 * (s + es) + 2.0 ** -25, rel=1e-12)
+    assert float(kc.conv_bound(x, w, b, r1, None, 2, torch.float32, operand_rel=2.0 ** -16)) == \
+        pytest.approx(e + 2.0 ** -16 * 1.0, rel=1e-12)
