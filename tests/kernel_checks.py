@@ -15,6 +15,11 @@ plant the defects the GPU tests are there to catch (tests/test_kernel_checks.py 
 The last section is the same for the DPT convolutions: integer and tap-mask operands (the tap mask names, per output
 element, the taps that fell inside the image), conv_bound, conv_emulation, and ConvLaunch, which calls the C entry
 points with pointers into Guarded buffers.
+
+The section after it serves the prologue and output kernels (prologue.hip): fp64 references of the vertex-normal
+encoding, the RoPE positions and register centres, the HDR decode, the texture Linear and the ray tokens, a bound
+beside each, LIBM_ULPS (the one assumed figure: the device math library's accuracy) and fp32 emulations with planted
+defects.
 """
 import math
 
@@ -656,3 +661,383 @@ def conv1x1_group_launch(members) -> None:
          arr(ctypes.c_void_p, [_gptr(m.bias) for m in members]), arr(ctypes.c_void_p, [_gptr(m.p_hi) for m in members]),
          arr(ctypes.c_int, [m.plane_ld for m in members]), m0.n, m0.h, m0.w, stream())
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------ prologue and output
+# Everything below serves prologue.hip (scene -> stage-1 tokens and RoPE positions, cameras -> ray tokens, logits ->
+# HDR frame): fp64 references computed from the fp32 inputs the kernels read, a bound next to each that counts one
+# F32_ULP per fp32 operation of the kernel's chain (FMA contraction only removes roundings), and fp32 emulations of
+# the kernels' order of operations with switches that plant one defect each.
+#
+# What this project cannot derive is the accuracy of the device math library (sinf, tanf, log10f, expm1f, powf).
+# LIBM_ULPS is the number of fp32 ulps of the result allowed per library call.  ASSUMED: the ROCm installation this
+# was written against ships no math-accuracy table, so the value is 4, which is at or above the figures the HIP
+# documentation has published for these five functions; the GPU tests print the share of each bound that is used.
+LIBM_ULPS = 4
+_HALF_PI = math.pi / 2.0
+_SIN_ABS = LIBM_ULPS * 2.0 ** -24  # LIBM_ULPS ulps of a sine: |sin| <= 1, so an ulp is at most 2^-24
+
+
+def _f32(v: float) -> float:
+    """The fp32 value a kernel receives for the host float v, as a Python float."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+# ---- vertex normals
+def _vn_scaled(vn: torch.Tensor, n_freqs: int) -> torch.Tensor:
+    """fp64 [n, 9 L]: x_d 2^l, d-major and l-minor (exact in fp32 as well: a power-of-two scale)."""
+    x = vn.double().reshape(-1, 9)
+    return (x[:, :, None] * 2.0 ** torch.arange(n_freqs, dtype=torch.float64)).reshape(-1, 9 * n_freqs)
+
+
+def vn_encode_ref(vn: torch.Tensor, n_freqs: int, ld: int) -> torch.Tensor:
+    """fp64 [n, ld]: [x | sin(x_d 2^l) | sin(x_d 2^l + pi / 2)], zero-padded to ld (rf.h, rf_ref.nerf_encode)."""
+    x, s, ns = vn.double().reshape(-1, 9), _vn_scaled(vn, n_freqs), 9 * n_freqs
+    assert ld >= 9 + 2 * ns
+    out = torch.zeros(x.shape[0], ld, dtype=torch.float64)
+    out[:, :9], out[:, 9:9 + ns], out[:, 9 + ns:9 + 2 * ns] = x, torch.sin(s), torch.sin(s + _HALF_PI)
+    return out
+
+
+def vn_encode_bound(vn: torch.Tensor, n_freqs: int, ld: int, out_dtype: torch.dtype) -> torch.Tensor:
+    """x is copied and x_d 2^l is exact; a sine term is one library call: LIBM_ULPS 2^-24; a phase-shifted term first
+    rounds s + fl(pi / 2), one F32_ULP of a sum below |s| + 2 (which also covers fl(pi / 2) - pi / 2 = 4.4e-8), and
+    |sin'| <= 1 carries that into the result: F32_ULP (|s| + 2) + LIBM_ULPS 2^-24.  The padding is exactly 0.  Then
+    the output rounding."""
+    s, ns = _vn_scaled(vn, n_freqs), 9 * n_freqs
+    e = torch.zeros(s.shape[0], ld, dtype=torch.float64)
+    e[:, 9:9 + ns] = _SIN_ABS
+    e[:, 9 + ns:9 + 2 * ns] = F32_ULP * (s.abs() + 2.0) + _SIN_ABS
+    return e + out_rounding(vn_encode_ref(vn, n_freqs, ld).abs(), e, out_dtype)
+
+
+def vn_encode_emulation(vn: torch.Tensor, n_freqs: int, ld: int, out_dtype: torch.dtype, freq_off_by_one=None,
+                        swap_sin_cos: bool = False, dirty_padding: bool = False) -> torch.Tensor:
+    """vn_encode_kernel in fp32.  Planted defects: freq_off_by_one = d takes 2^(l + 1) for input dimension d only;
+    swap_sin_cos writes the phase-shifted block first; dirty_padding leaves the smallest fp16 subnormal (what a
+    buffer that held other data would show is larger) in the columns past 9 (2 L + 1)."""
+    x, ns = vn.float().reshape(-1, 9), 9 * n_freqs
+    lvl = torch.arange(n_freqs, dtype=torch.float32).expand(9, n_freqs).clone()
+    if freq_off_by_one is not None:
+        lvl[freq_off_by_one] += 1.0
+    s = (x[:, :, None] * torch.exp2(lvl)).reshape(-1, ns)
+    a, b = torch.sin(s), torch.sin(s + torch.tensor(_HALF_PI, dtype=torch.float32))
+    if swap_sin_cos:
+        a, b = b, a
+    out = torch.full((x.shape[0], ld), 2.0 ** -24 if dirty_padding else 0.0, dtype=torch.float32)
+    out[:, :9], out[:, 9:9 + ns], out[:, 9 + ns:9 + 2 * ns] = x, a, b
+    return out.to(out_dtype)
+
+
+# ---- RoPE positions and register-token centres
+def _scene_sets(scene_off, c2w, n_views: int):
+    off = [int(v) for v in scene_off]
+    n_scenes = len(off) - 1
+    sets = n_scenes * n_views if c2w is not None else n_scenes
+    return off, [(s // n_views if c2w is not None else s) for s in range(sets)]
+
+
+def scene_pos_ref(tris, valid_idx, scene_off, c2w, n_views: int, n_reg: int):
+    """(rows, centres) in fp64.  rows: one [n_s, 9] tensor per set (set s = scene b without c2w, else b n_views + v):
+    the scene's valid triangles, with c2w [sets, 4, 4] each vertex p as R^T (p - t).  centres [sets, 3]: per
+    coordinate sum / (n + 1e-5) over the set's rows, averaged over the three vertices (rf.h; n_reg rows of
+    [c | c | c] precede the triangle rows in pos_out: scene_pos_pack)."""
+    off, scene_of = _scene_sets(scene_off, c2w, n_views)
+    t64, idx = tris.double().reshape(-1, 9), valid_idx.long()
+    rows, centres = [], []
+    for s, b in enumerate(scene_of):
+        v = t64[idx[off[b]:off[b + 1]]]
+        if c2w is not None:
+            m = c2w.double().reshape(-1, 4, 4)[s]
+            v = ((v.view(-1, 3, 3) - m[:3, 3]) @ m[:3, :3]).reshape(-1, 9)  # (R^T p)_a = sum_b R_ba p_b: p @ R
+        rows.append(v)
+        centres.append((v.sum(0) / (v.shape[0] + 1e-5)).view(3, 3).mean(0))
+    return rows, torch.stack(centres)
+
+
+def scene_pos_bound(tris, valid_idx, scene_off, c2w, n_views: int, n_reg: int):
+    """(row bounds, centre bounds), shaped as scene_pos_ref's results.
+    Rows: a copy without c2w (bound 0).  With it the kernel forms tinv_a = -(sum_b R_ba t_b), 3 products and 2 adds,
+    then sum_b R_ba p_b + tinv_a, 3 products and 3 adds, every one within one F32_ULP of a partial sum that is at
+    most Mp + Mt (Mp = sum_b |R_ba| |p_b|, Mt = sum_b |R_ba| |t_b|; Mt alone for tinv): F32_ULP (6 (Mp + Mt) + 5 Mt).
+    Centres: the issue's count, (6 + 2 + nb + 4) 2^-24 mean|x| with nb = ceil(n / 256): every add is correctly
+    rounded (2^-24 relative) and an element passes through the 6 butterfly adds of its wave, the 2 adds over the 4
+    waves, the nb - 1 serial adds over the blocks (the first adds to 0: exact), and then fl(n + 1e-5), the division,
+    two vertex adds and the division by 3.  mean|x| = sum |x| / (n + 1e-5) averaged over the three vertices bounds
+    every partial sum of that chain; the rows' own error enters the sum the same way (their bound, averaged)."""
+    off, scene_of = _scene_sets(scene_off, c2w, n_views)
+    rows, _ = scene_pos_ref(tris, valid_idx, scene_off, c2w, n_views, n_reg)
+    t64, idx = tris.double().reshape(-1, 9), valid_idx.long()
+    e_rows, e_centres = [], []
+    for s, b in enumerate(scene_of):
+        v = t64[idx[off[b]:off[b + 1]]]
+        e = torch.zeros_like(v)
+        if c2w is not None:
+            m = c2w.double().reshape(-1, 4, 4)[s].abs()
+            mp, mt = v.abs().view(-1, 3, 3) @ m[:3, :3], m[:3, 3] @ m[:3, :3]
+            e = (F32_ULP * (6.0 * (mp + mt) + 5.0 * mt)).reshape(-1, 9)
+        n = v.shape[0]
+        ops = 6 + 2 + (n + 255) // 256 + 4
+        mean_abs = ((rows[s].abs() + e).sum(0) / (n + 1e-5)).view(3, 3).mean(0)
+        e_rows.append(e)
+        e_centres.append(ops * 2.0 ** -24 * mean_abs + (e.sum(0) / (n + 1e-5)).view(3, 3).mean(0))
+    return e_rows, torch.stack(e_centres)
+
+
+def scene_pos_pack(rows, centres, n_reg: int):
+    """pos_out's layout from per-set rows and centres: ([total, 9] fp64, set_off int32 [sets + 1], centre-row mask)."""
+    parts, off, is_centre = [], [0], []
+    for r, c in zip(rows, centres):
+        parts += [c.repeat(3)[None].expand(n_reg, 9), r]
+        is_centre += [torch.ones(n_reg, dtype=torch.bool), torch.zeros(r.shape[0], dtype=torch.bool)]
+        off.append(off[-1] + n_reg + r.shape[0])
+    return torch.cat(parts), torch.tensor(off, dtype=torch.int32), torch.cat(is_centre)
+
+
+def scene_centre_emulation(rows: torch.Tensor, drop_second_round: bool = False, divide_by_n: bool = False):
+    """The centre [3] of one set's rows [n, 9] in fp32 in the kernels' order: per block of 256 the xor butterfly of each
+    64-lane wave (wave_sum), (w0 + w1) + (w2 + w3), then the block partials serially in block order, / (n + 1e-5),
+    the three vertices added and / 3.  Planted defects: drop_second_round stops after the first 64 blocks;
+    divide_by_n divides by n (0 / 0 in an empty set)."""
+    n = rows.shape[0]
+    nb = (n + 255) // 256
+    v = torch.zeros(max(nb, 1) * 256, 9, dtype=torch.float32)
+    v[:n] = rows.float()
+    v = v.view(-1, 4, 64, 9)
+    lane = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ o]
+    w = v[:, :, 0]
+    part = (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+    acc = torch.zeros(9, dtype=torch.float32)
+    for b in range(min(nb, 64) if drop_second_round else nb):
+        acc = acc + part[b]
+    den = torch.tensor(float(n), dtype=torch.float32)
+    tot = acc / (den if divide_by_n else den + torch.tensor(1e-5, dtype=torch.float32))
+    return (tot[0:3] + tot[3:6] + tot[6:9]) / torch.tensor(3.0, dtype=torch.float32)
+
+
+# ---- HDR output
+def hdr_ref(logits: torch.Tensor, alpha: float, log_decode: bool, channels_last: bool) -> torch.Tensor:
+    """fp64 decode(elu(logits [n, c, h, w], fl32(alpha))), decode = 10^y - 1 if log_decode; [n, h, w, c] when
+    channels_last.  A window of the output is this function of the same window of the logits."""
+    y = logits.double()
+    y = torch.where(y > 0, y, _f32(alpha) * torch.expm1(y))
+    if log_decode:
+        y = torch.pow(10.0, y) - 1.0
+    return (y.permute(0, 2, 3, 1) if channels_last else y).contiguous()
+
+
+def hdr_bound(logits: torch.Tensor, alpha: float, log_decode: bool, channels_last: bool) -> torch.Tensor:
+    """y > 0 passes through.  Otherwise alpha expm1f(y): the library call within LIBM_ULPS ulps of its result and one
+    multiply: e1 = (LIBM_ULPS + 1) F32_ULP |elu|.  Log decode: powf within LIBM_ULPS ulps of 10^y', y' within e1 of
+    y (10^y (10^e1 - 1) exactly), and the subtraction one ulp of its result:
+    10^y (10^e1 - 1) + LIBM_ULPS F32_ULP 10^y + F32_ULP |10^y - 1|."""
+    x = logits.double()
+    y = torch.where(x > 0, x, _f32(alpha) * torch.expm1(x))
+    e = torch.where(x > 0, torch.zeros_like(y), (LIBM_ULPS + 1) * F32_ULP * y.abs())
+    if log_decode:
+        p = torch.pow(10.0, y)
+        e = p * (torch.pow(10.0, e) - 1.0) + LIBM_ULPS * F32_ULP * p + F32_ULP * (p - 1.0).abs()
+    return (e.permute(0, 2, 3, 1) if channels_last else e).contiguous()
+
+
+def hdr_emulation(logits: torch.Tensor, alpha: float, log_decode: bool, channels_last: bool,
+                  wrong_layout_index: bool = False, exp_for_expm1: bool = False) -> torch.Tensor:
+    """hdr_output_kernel in fp32.  Planted defects: wrong_layout_index stores a channels-last output at the
+    channels-first index (img c + ch) hw + px; exp_for_expm1 computes alpha exp(y) on the negative branch."""
+    x = logits.float()
+    a = torch.tensor(alpha, dtype=torch.float32)
+    y = torch.where(x > 0, x, a * (torch.exp(x) if exp_for_expm1 else torch.expm1(x)))
+    if log_decode:
+        y = torch.pow(torch.tensor(10.0, dtype=torch.float32), y) - 1.0
+    n, c, h, w = y.shape
+    if channels_last and wrong_layout_index:
+        return y.contiguous().view(n, h, w, c)
+    return (y.permute(0, 2, 3, 1) if channels_last else y).contiguous()
+
+
+# ---- texture encoder
+def log_encode_ref(x: torch.Tensor):
+    """(fp64 log10(fl32(x + 1)), its bound): the add is the kernel's own fp32 operation, so only the library call is
+    left: LIBM_ULPS ulps of the result."""
+    ref = torch.log10((x.float() + 1.0).double())
+    return ref, LIBM_ULPS * F32_ULP * ref.abs()
+
+
+def texture_linear_ref(coef: torch.Tensor, wsum: torch.Tensor, bias) -> torch.Tensor:
+    """fp64 [rows, n] = bias + coef[:, :channels] wsum (wsum [channels, n])."""
+    ref = coef[:, :wsum.shape[0]].double() @ wsum.double()
+    return ref if bias is None else ref + bias.double()
+
+
+def texture_linear_bound(coef: torch.Tensor, wsum: torch.Tensor, bias) -> torch.Tensor:
+    """The accumulator starts at the bias and takes one fused multiply-add per channel (the padded channels add an
+    exact 0): `channels` roundings, each within one F32_ULP of a partial sum of at most |bias| + |coef| |wsum|."""
+    ch = wsum.shape[0]
+    mag = coef[:, :ch].double().abs() @ wsum.double().abs()
+    return ch * F32_ULP * (mag if bias is None else mag + bias.double().abs())
+
+
+def texture_linear_emulation(coef, wsum, bias, bias_per_trip: bool = False,
+                             skip_last_partial_block: bool = False) -> torch.Tensor:
+    """texture_linear_kernel in fp32: acc = bias, then acc = fma(coef[r, c], wsum[c, o], acc) in channel order (the
+    product exact in fp64, the sum rounded to fp32).  Unwritten elements are NaN.  Planted defects: bias_per_trip adds
+    the bias once per 1024-column trip of a thread, so columns 1024 t .. 1024 t + 1023 get it t + 1 times;
+    skip_last_partial_block leaves the rows of a last block of fewer than 16 rows unwritten."""
+    ch, n = wsum.shape
+    rows = coef.shape[0]
+    b = torch.zeros(n, dtype=torch.float32) if bias is None else bias.float()
+    acc = b.expand(rows, n).clone()
+    if bias_per_trip:
+        acc = acc * (1 + torch.arange(n) // 1024).float()
+    for c in range(ch):
+        acc = (acc.double() + coef[:, c:c + 1].double() * wsum[c].double()).float()
+    if skip_last_partial_block and rows % 16:
+        acc[rows - rows % 16:] = float("nan")
+    return acc
+
+
+# ---- rays
+def patchify_ref(rays: torch.Tensor, patch: int) -> torch.Tensor:
+    """[v, h, w, 3] -> tokens [v (h / p) (w / p), 3 p p]: out[view R + py (w / p) + px, c p p + p1 p + p2] (rf.h)."""
+    v, h, w, _ = rays.shape
+    p = patch
+    return rays.view(v, h // p, p, w // p, p, 3).permute(0, 1, 3, 5, 2, 4).reshape(v * (h // p) * (w // p), 3 * p * p)
+
+
+def ray_tokens_ref(c2w, fov, intr, frame, token_frame, origin, patch: int, out_dtype: torch.dtype = None):
+    """(tokens fp64, ray_pos fp64 [v, 9], bound or None) by the formula of rf.h: token pixel (x, y) of the h x w token
+    frame is pixel (x - x0, y - y0) of the requested frame_h x frame_w frame's camera; direction ((x' + 0.5 - cx) / fx,
+    -(y' + 0.5 - cy) / fy, -1) rotated by c2w and L2-normalised; fov mode (degrees, vertical): fx = fy = frame_h / 2 /
+    tan(fov / 2), cx = frame_w / 2, cy = frame_h / 2; intr [v, 4] = (fx, fy, cx, cy).  ray_pos = the camera origin
+    three times.
+    bound (with out_dtype), one F32_ULP per operation, to first order:
+      f       fov / 180, * pi (fl(pi) is within 2^-24 of pi), tanf, the division: the argument's 2 F32_ULP pass
+              through tan as theta (1 + t^2) / t relative, plus LIBM_ULPS + 1 ulps: rel_f (0 with intrinsics);
+      dx, dy  the subtraction of cx rounds once, F32_ULP (|x' + 0.5| + |cx|), then the division: e_d = (e_num + |num|
+              (F32_ULP + rel_f)) / |f|;
+      r_a     3 products and 2 adds within F32_ULP of Mr = |dx| |m0| + |dy| |m1| + |m2|, plus the inputs' errors;
+      nrm     3 products, 2 adds (5 F32_ULP of nrm^2, plus 2 sum |r_a| e_a), the square root halves that and adds one;
+      out     r_a / nrm: e_a / nrm + |r_a| / nrm (rel_nrm + F32_ULP); then the output rounding."""
+    m = c2w.double().reshape(-1, 4, 4)
+    nv = m.shape[0]
+    (fh, fw), (h, w), (y0, x0) = frame, token_frame, origin
+    if intr is not None:
+        k = intr.double().reshape(nv, 4)
+        fx, fy, cx, cy = k[:, 0], k[:, 1], k[:, 2], k[:, 3]
+        rel_f = torch.zeros(nv, dtype=torch.float64)
+    else:
+        theta = 0.5 * (fov.double().reshape(nv) / 180.0 * math.pi)
+        t = torch.tan(theta)
+        fx = fy = fh / 2.0 / t
+        cx, cy = torch.full((nv,), fw / 2.0, dtype=torch.float64), torch.full((nv,), fh / 2.0, dtype=torch.float64)
+        rel_f = F32_ULP * (2.0 * theta * (1.0 + t * t) / t + LIBM_ULPS + 1.0)
+    xs = (torch.arange(w, dtype=torch.float64) - x0 + 0.5)[None, None, :]
+    ys = (torch.arange(h, dtype=torch.float64) - y0 + 0.5)[None, :, None]
+    v3 = lambda a: a[:, None, None]  # noqa: E731  ([v] -> [v, 1, 1])
+    nx, ny = (xs - v3(cx)).expand(nv, h, w), (ys - v3(cy)).expand(nv, h, w)
+    dx, dy = nx / v3(fx), -(ny / v3(fy))
+    d = torch.stack([dx, dy, -torch.ones_like(dx)], dim=-1)  # [v, h, w, 3]
+    rot = m[:, :3, :3]
+    r = torch.einsum("vhwb,vab->vhwa", d, rot)
+    nrm = r.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    rays = r / nrm
+    ray_pos = m[:, :3, 3].repeat(1, 3)
+    bound = None
+    if out_dtype is not None:
+        e_dx = (F32_ULP * (xs.abs() + v3(cx).abs()) + nx.abs() * (F32_ULP + v3(rel_f))) / v3(fx).abs()
+        e_dy = (F32_ULP * (ys.abs() + v3(cy).abs()) + ny.abs() * (F32_ULP + v3(rel_f))) / v3(fy).abs()
+        e_d = torch.stack([e_dx.expand(nv, h, w), e_dy.expand(nv, h, w), torch.zeros(nv, h, w, dtype=torch.float64)], -1)
+        e_r = 5.0 * F32_ULP * torch.einsum("vhwb,vab->vhwa", d.abs(), rot.abs()) + \
+            torch.einsum("vhwb,vab->vhwa", e_d, rot.abs())
+        rel_n = 0.5 * (5.0 * F32_ULP + 2.0 * (r.abs() * e_r).sum(-1, keepdim=True) / (nrm * nrm)) + F32_ULP
+        e = e_r / nrm + rays.abs() * (rel_n + F32_ULP)
+        bound = patchify_ref(e + out_rounding(rays.abs(), e, out_dtype), patch)
+    return patchify_ref(rays, patch), ray_pos, bound
+
+
+# ---- the inputs the GPU tests run and the CPU proofs plant their defects into
+VN_ROWS = (1, 6, 257)  # one row, 4 < n < 8 (a ragged second block), 64 blocks and one row
+VN_SHAPES = ((6, 128), (6, 117), (6, 192), (1, 27), (1, 32))  # (L, ldo); L = 1: n_sin = 9
+SCENE_COUNTS = (16700, 0, 256, 257)  # 66 blocks (two rounds of the centre kernel), empty, 256 k, 256 k + 1
+SCENE_COUNTS_VIEWS = (300, 0, 513)  # with c2w and 3 views
+HDR_SHAPES = ((1, 1, 1), (1, 15, 17), (1, 1, 257), (2, 3, 7))  # (n, h, w): 1, 255, 257 and 42 pixels
+HDR_SPECIALS = (0.0, -0.0, 1e-8, -1e-8, -50.0, 10.0, -1e-3)
+TEXTURE_LINEAR_SHAPES = ((1, 1, 4), (17, 13, 1024), (33, 16, 1028), (16, 13, 2048))  # (rows, channels, n)
+
+
+def vn_case(n_rows: int, seed: int = 0):
+    """(vn f32 [n_rows, 9], dst_row int32 [n_rows], written bool [n_rows]).  Unit normals, three to a row; row 0 starts
+    with the exact values 1, -1, 0, -0.0 and row 3 (if there is one) holds nothing else.  dst_row sends every input
+    row to a row of its own of an n_rows-row output, in shuffled order, except every fifth one (from row 2), which is a
+    hole (-1): `written` marks the output rows that receive a row."""
+    g = torch.Generator(device="cpu").manual_seed(1000 + seed)
+    v = torch.randn(n_rows, 3, 3, generator=g)
+    vn = (v / v.norm(dim=-1, keepdim=True)).reshape(n_rows, 9).contiguous()
+    vn[0, :4] = torch.tensor([1.0, -1.0, 0.0, -0.0])
+    if n_rows > 3:
+        vn[3] = torch.tensor([1.0, 0.0, -0.0, -1.0, 0.0, 1.0, -0.0, -1.0, 0.0])
+    dst = torch.randperm(n_rows, generator=g).to(torch.int32)
+    dst[2::5] = -1
+    written = torch.zeros(n_rows, dtype=torch.bool)
+    written[dst[dst >= 0].long()] = True
+    return vn, dst, written
+
+
+def vn_scatter(values: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """values [n, ld] of the input rows -> the output's rows (unwritten rows 0; compare written rows only)."""
+    out = torch.zeros_like(values)
+    keep = dst >= 0
+    out[dst[keep].long()] = values[keep]
+    return out
+
+
+def scene_case(counts, n_views: int = 0, seed: int = 0):
+    """(tris f32 [m, 9], valid_idx int32, scene_off int32, c2w f32 [scenes n_views, 4, 4] or None).  The valid rows are
+    a shuffled subset of the m rows of tris (a mask with holes, its rows in no order); the rows outside it are NaN.
+    Vertices are normal around (0.3, -0.2, 0.5), so no centre is a sum that cancels.  c2w: a random rotation (QR of a
+    normal matrix, determinant +1: no axis-aligned or symmetric R, so a transposed R shows) and a translation of a few
+    units per view."""
+    g = torch.Generator(device="cpu").manual_seed(2000 + seed)
+    total = sum(counts)
+    m = total + total // 4 + 7
+    valid = torch.randperm(m, generator=g)[:total]
+    tris = torch.full((m, 9), float("nan"))
+    tris[valid] = 0.5 * torch.randn(total, 9, generator=g) + torch.tensor([0.3, -0.2, 0.5]).repeat(3)
+    scene_off = torch.tensor([0] + torch.tensor(counts).cumsum(0).tolist(), dtype=torch.int32)
+    c2w = None
+    if n_views:
+        sets = len(counts) * n_views
+        q, r = torch.linalg.qr(torch.randn(sets, 3, 3, generator=g).double())
+        q = q * torch.sign(torch.diagonal(r, dim1=-2, dim2=-1))[:, None, :]
+        q[:, :, 0] *= torch.linalg.det(q)[:, None]
+        c2w = torch.eye(4).repeat(sets, 1, 1)
+        c2w[:, :3, :3] = q.float()
+        c2w[:, :3, 3] = 2.0 * torch.randn(sets, 3, generator=g) + torch.tensor([1.0, -3.0, 2.0])
+    return tris, valid.to(torch.int32), scene_off, c2w
+
+
+def hdr_logits(n: int, c: int, h: int, w: int, seed: int = 0) -> torch.Tensor:
+    """Normal logits (sigma 2) [n, c, h, w] whose first elements are HDR_SPECIALS (as many as fit)."""
+    g = torch.Generator(device="cpu").manual_seed(3000 + seed)
+    x = 2.0 * torch.randn(n, c, h, w, generator=g)
+    k = min(x.numel(), len(HDR_SPECIALS))
+    x.view(-1)[:k] = torch.tensor(HDR_SPECIALS[:k])
+    return x
+
+
+def texture_linear_case(rows: int, channels: int, n: int, seed: int = 0):
+    """(coef f32 [rows, channels], wsum f32 [channels, n], bias f32 [n]), normal."""
+    g = torch.Generator(device="cpu").manual_seed(4000 + seed)
+    return torch.randn(rows, channels, generator=g), torch.randn(channels, n, generator=g), torch.randn(n, generator=g)
+
+
+def camera_case(n_views: int, seed: int = 0):
+    """(c2w f32 [v, 4, 4], fov degrees f32 [v] in [25, 70], intr f32 [v, 4] = (fx, fy, cx, cy) for a frame of about
+    24 x 40 pixels, fx != fy and the principal point off the centre)."""
+    g = torch.Generator(device="cpu").manual_seed(5000 + seed)
+    c2w = scene_case((1,), n_views, seed)[3]
+    fov = 25.0 + 45.0 * torch.rand(n_views, generator=g)
+    intr = torch.tensor([30.0, 33.0, 19.0, 13.0]) + torch.rand(n_views, 4, generator=g) * torch.tensor([9.0, 9.0, 3.0, 3.0])
+    return c2w, fov, intr

@@ -6,7 +6,10 @@ input padding) is flagged by the helper the GPU tests use, and the unmodified em
 last section does the same for the convolution helpers: a dropped 32-channel chunk of one tap at one pixel, a halo
 column read as zero, a row read from the previous image, a wrong border class and a store past cout are each flagged
 by the exact form, the tap mask, conv_bound or the guard band -- and the first of them passes the whole-tensor
-`relerr < 1e-3` plane bar of the older conv tests.
+`relerr < 1e-3` plane bar of the older conv tests.  The section after it covers the prologue and output kernels: each
+emulation passes its bound, each planted defect (a frequency index off by one, swapped sine blocks, dirty padding, a
+dropped reduction round, a division by n, a channels-first index, exp for expm1, a bias added per trip, a skipped
+partial block) fails it, and the fp32 oracle lies inside the bounds of the fp64 references.
 """
 import math
 
@@ -426,3 +429,175 @@ def test_conv_bound_terms():
         pytest.approx(es + 2.0 ** -11 * (s + es) + 2.0 ** -25, rel=1e-12)
     assert float(kc.conv_bound(x, w, b, r1, None, 2, torch.float32, operand_rel=2.0 ** -16)) == \
         pytest.approx(e + 2.0 ** -16 * 1.0, rel=1e-12)
+
+
+# ------------------------------------------------------------------------------------------------ prologue and output
+# The references, bounds and emulations of the prologue kernels, at the shapes tests/test_prologue_exact_gpu.py runs:
+# every clean emulation passes its check, every planted defect fails it, and the fp32 oracle (which the goldens pin to
+# the reference project) lies inside the bounds of the fp64 references.
+def _vn_check(out, vn, dst, written, n_freqs, ld, dtype, what=""):
+    ref = kc.vn_scatter(kc.vn_encode_ref(vn, n_freqs, ld), dst)
+    bound = kc.vn_scatter(kc.vn_encode_bound(vn, n_freqs, ld, dtype), dst)
+    return kc.assert_elementwise(out[written], ref[written], bound[written], what)
+
+
+@pytest.mark.parametrize("dtype", HALF)
+@pytest.mark.parametrize("n_freqs,ld", kc.VN_SHAPES)
+@pytest.mark.parametrize("n_rows", kc.VN_ROWS)
+def test_vn_encode_emulation_and_its_planted_defects(n_rows, n_freqs, ld, dtype):
+    vn, dst, written = kc.vn_case(n_rows)
+    assert n_rows == 1 or not bool(written.all()), "the case must have holes"
+    clean = kc.vn_scatter(kc.vn_encode_emulation(vn, n_freqs, ld, dtype), dst)
+    ratio = _vn_check(clean, vn, dst, written, n_freqs, ld, dtype, "clean")
+    assert 0.0 < ratio <= 1.0
+    defects = [{"freq_off_by_one": 8}, {"swap_sin_cos": True}]
+    if ld > 9 * (2 * n_freqs + 1):
+        defects.append({"dirty_padding": True})
+    for kw in defects:
+        bad = kc.vn_scatter(kc.vn_encode_emulation(vn, n_freqs, ld, dtype, **kw), dst)
+        with pytest.raises(AssertionError, match="beyond their bound"):
+            _vn_check(bad, vn, dst, written, n_freqs, ld, dtype, str(kw))
+
+
+def test_vn_encode_older_bar_passes_a_wrong_frequency_on_small_values():
+    """Why atol = 1e-2 on bf16 was not enough: the frequency index off by one in the lowest level of one input dimension
+    moves sin(x) to sin(2 x), which for |x| < 1e-2 is a change below 1e-2 -- and beyond the per-element bound."""
+    vn = torch.full((4, 9), 2.0 ** -7)
+    bad = kc.vn_encode_emulation(vn, 6, 128, torch.bfloat16, freq_off_by_one=0)
+    ref = kc.vn_encode_ref(vn, 6, 128)
+    assert float((bad.double() - ref.to(torch.bfloat16).double()).abs()[:, 9].max()) < 1e-2
+    with pytest.raises(AssertionError, match="beyond their bound"):
+        kc.assert_elementwise(bad, ref, kc.vn_encode_bound(vn, 6, 128, torch.bfloat16))
+
+
+def test_nerf_encode_oracle_lies_inside_the_vn_bound():
+    g = torch.Generator(device="cpu").manual_seed(11)
+    v = torch.randn(5000, 3, 3, generator=g)
+    vn = (v / v.norm(dim=-1, keepdim=True)).reshape(5000, 9)
+    from oracle import rf_ref
+    ratio = kc.assert_elementwise(rf_ref.nerf_encode(vn, 6), kc.vn_encode_ref(vn, 6, 117),
+                                  kc.vn_encode_bound(vn, 6, 117, torch.float32), "oracle")
+    print(f"nerf_encode oracle: worst |err| / bound {ratio:.3f}")
+    assert 0.0 < ratio < 0.5
+
+
+def _centres_f32(rows, **kw):
+    return torch.stack([kc.scene_centre_emulation(r, **kw) for r in rows])
+
+
+@pytest.mark.parametrize("counts,n_views", [(kc.SCENE_COUNTS, 0), (kc.SCENE_COUNTS_VIEWS, 3)])
+def test_scene_centre_emulation_and_its_planted_defects(counts, n_views):
+    tris, valid, off, c2w = kc.scene_case(counts, n_views)
+    rows, centres = kc.scene_pos_ref(tris, valid, off, c2w, n_views, 16)
+    e_rows, e_centres = kc.scene_pos_bound(tris, valid, off, c2w, n_views, 16)
+    assert len(rows) == len(counts) * max(n_views, 1) and [r.shape[0] for r in rows[::max(n_views, 1)]] == list(counts)
+    assert all(bool(torch.isfinite(r).all()) for r in rows), "no hole of the mask among the valid rows"
+    f32_rows = [r.float() for r in rows]  # (the kernel's rows, up to their own bound, which e_centres carries)
+    ratio = kc.assert_elementwise(_centres_f32(f32_rows), centres, e_centres, "clean")
+    assert ratio < 0.5
+    empty = counts.index(0) * max(n_views, 1)
+    assert float(centres[empty].abs().max()) == 0.0 and float(e_centres[empty].max()) == 0.0  # exactly 0 / 1e-5
+    with pytest.raises(AssertionError, match=rf"worst at \({empty}, "):
+        kc.assert_elementwise(_centres_f32(f32_rows, divide_by_n=True), centres, e_centres, "divide_by_n")
+    if max(counts) > 64 * 256:
+        with pytest.raises(AssertionError, match=r"worst at \(0, "):
+            kc.assert_elementwise(_centres_f32(f32_rows, drop_second_round=True), centres, e_centres, "second round")
+
+
+def test_oracle_positions_lie_inside_the_scene_bounds():
+    """rf_ref.center_pos (no c2w, 66 blocks) and rf_ref.cam_transform + center_pos (3 views) against scene_pos_ref."""
+    from oracle import rf_ref
+    for counts, n_views in ((kc.SCENE_COUNTS, 0), (kc.SCENE_COUNTS_VIEWS, 3)):
+        tris, valid, off, c2w = kc.scene_case(counts, n_views)
+        rows, centres = kc.scene_pos_ref(tris, valid, off, c2w, n_views, 16)
+        e_rows, e_centres = kc.scene_pos_bound(tris, valid, off, c2w, n_views, 16)
+        nmax, v = max(counts), max(n_views, 1)
+        pos = torch.zeros(len(counts), nmax, 9)
+        mask = torch.zeros(len(counts), nmax, dtype=torch.bool)
+        for b, n in enumerate(counts):
+            pos[b, :n] = tris[valid[int(off[b]):int(off[b + 1])].long()]
+            mask[b, :n] = True
+        if n_views:
+            pos = rf_ref.cam_transform(c2w, torch.repeat_interleave(pos, v, 0).view(-1, nmax, 3, 3)).reshape(-1, nmax, 9)
+            mask = torch.repeat_interleave(mask, v, 0)
+        got, _ = rf_ref.center_pos(pos * mask[..., None], mask, 16)
+        for s, r in enumerate(rows):
+            n = r.shape[0]
+            worst_r = kc.assert_elementwise(got[s, 16:16 + n], r, e_rows[s], f"oracle rows of set {s}")
+            worst_c = kc.assert_elementwise(got[s, :16], centres[s].repeat(3).expand(16, 9),
+                                            e_centres[s].repeat(3).expand(16, 9), f"oracle centre of set {s}")
+            assert worst_c <= 0.5 and worst_r <= 0.5
+
+
+@pytest.mark.parametrize("log_decode", [True, False])
+@pytest.mark.parametrize("channels_last", [True, False])
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("n,h,w", kc.HDR_SHAPES)
+def test_hdr_emulation_and_its_planted_defects(n, h, w, c, channels_last, log_decode):
+    x = kc.hdr_logits(n, c, h, w)
+    ref, bound = kc.hdr_ref(x, 1e-3, log_decode, channels_last), kc.hdr_bound(x, 1e-3, log_decode, channels_last)
+    assert ref.shape == ((n, h, w, c) if channels_last else (n, c, h, w))
+    ratio = kc.assert_elementwise(kc.hdr_emulation(x, 1e-3, log_decode, channels_last), ref, bound, "clean")
+    assert ratio <= 1.0
+    if n * h * w * c >= 5:  # (an element of the negative branch is among the specials)
+        with pytest.raises(AssertionError, match="beyond their bound"):
+            kc.assert_elementwise(kc.hdr_emulation(x, 1e-3, log_decode, channels_last, exp_for_expm1=True), ref, bound)
+    if channels_last and c > 1 and h * w > 1:
+        with pytest.raises(AssertionError, match="beyond their bound"):
+            kc.assert_elementwise(kc.hdr_emulation(x, 1e-3, log_decode, True, wrong_layout_index=True), ref, bound)
+
+
+@pytest.mark.parametrize("with_bias", [True, False])
+@pytest.mark.parametrize("rows,channels,n", kc.TEXTURE_LINEAR_SHAPES)
+def test_texture_linear_emulation_and_its_planted_defects(rows, channels, n, with_bias):
+    coef, wsum, bias = kc.texture_linear_case(rows, channels, n)
+    bias = bias if with_bias else None
+    ref, bound = kc.texture_linear_ref(coef, wsum, bias), kc.texture_linear_bound(coef, wsum, bias)
+    ratio = kc.assert_elementwise(kc.texture_linear_emulation(coef, wsum, bias), ref, bound, "clean")
+    assert 0.0 < ratio <= 0.5
+    if rows % 16:
+        with pytest.raises(AssertionError, match=rf"worst at \({rows - rows % 16}, "):
+            kc.assert_elementwise(kc.texture_linear_emulation(coef, wsum, bias, skip_last_partial_block=True), ref, bound)
+    bad = kc.texture_linear_emulation(coef, wsum, bias, bias_per_trip=True)
+    if n > 1024 and with_bias:
+        with pytest.raises(AssertionError, match=r"worst at \(\d+, 1\d{3}\)"):
+            kc.assert_elementwise(bad, ref, bound)
+        kc.assert_elementwise(bad[:, :1024], ref[:, :1024], bound[:, :1024])  # the first trip is clean
+    else:
+        kc.assert_elementwise(bad, ref, bound)  # nothing to see without a second trip or a bias
+
+
+def test_texture_linear_defects_are_each_reached_by_a_gpu_shape():
+    shapes = kc.TEXTURE_LINEAR_SHAPES
+    assert any(n > 1024 for _, _, n in shapes) and any(r % 16 for r, _, _ in shapes) and any(r % 16 == 0 for r, _, _ in shapes)
+    assert {c for _, c, _ in shapes} >= {1, 16} and any(n < 1024 for _, _, n in shapes)
+
+
+def test_ray_gen_oracle_lies_inside_the_ray_bound():
+    """rf_ref.ray_gen (square frames, fov) against ray_tokens_ref; and the overscan identity of the reference itself:
+    the token frame's rays are the requested frame's rays where the two overlap."""
+    from oracle import rf_ref
+    c2w, fov, intr = kc.camera_case(3)
+    res, p = 24, 8
+    ro, rd = rf_ref.ray_gen(c2w, (fov / 180.0 * torch.pi)[:, None], res)
+    tok, pos, bound = kc.ray_tokens_ref(c2w, fov, None, (res, res), (res, res), (0, 0), p, torch.float32)
+    ratio = kc.assert_elementwise(kc.patchify_ref(rd, p), tok, bound, "oracle rays")
+    print(f"ray_gen oracle: worst |err| / bound {ratio:.3f}")
+    assert 0.0 < ratio <= 0.5
+    assert torch.equal(ro.repeat(1, 3).double(), pos)
+    inner, _, _ = kc.ray_tokens_ref(c2w, None, intr, (8, 24), (8, 24), (0, 0), p)
+    outer, _, _ = kc.ray_tokens_ref(c2w, None, intr, (8, 24), (24, 40), (8, 8), p)
+    assert torch.equal(outer.view(3, 3, 5, -1)[:, 1, 1:4], inner.view(3, 1, 3, -1)[:, 0])
+
+
+def test_ray_bound_flags_a_transposed_rotation_and_a_shifted_principal_point():
+    c2w, fov, intr = kc.camera_case(3)
+    for dtype in HALF:
+        tok, _, bound = kc.ray_tokens_ref(c2w, None, intr, (8, 24), (24, 40), (8, 8), 8, dtype)
+        kc.assert_elementwise(tok.to(dtype), tok, bound, "rounded reference")
+        c2w_t = c2w.clone()
+        c2w_t[:, :3, :3] = c2w[:, :3, :3].transpose(1, 2)
+        for bad in (kc.ray_tokens_ref(c2w_t, None, intr, (8, 24), (24, 40), (8, 8), 8)[0],
+                    kc.ray_tokens_ref(c2w, None, intr, (8, 24), (24, 40), (8, 7), 8)[0]):
+            with pytest.raises(AssertionError, match="beyond their bound"):
+                kc.assert_elementwise(bad.to(dtype), tok, bound)
