@@ -18,7 +18,10 @@ pinned host memory (texture kept in the dtype the file stores, widened on the de
 host-to-device copy runs on a side stream that the compute stream waits on, results come back on
 another side stream, and writer threads encode and write the EXR/PNG files — the GPU only waits for
 the HDF5 decode when that is slower than a batch.  RF_BATCH_INLINE=1 runs every step
-inline on the main thread.
+inline on the main thread.  With `--tone_mapper pbr_neutral` or `--exposure` the PNG's 8-bit frame
+is made on the device (pipeline.to_ldr) once the frame's fp16 range check is resolved, and comes
+back on the same side stream into pinned memory; without them the PNG is hdr_to_ldr of the host
+frame, as before.
 """
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from infer import PRECISION, add_common_args, frame_resolution, load_pipeline, save_views
+from infer import PRECISION, add_common_args, device_ldr, frame_resolution, load_pipeline, save_views
 from renderformer_amd.h5io import File
 from renderformer_amd.parallel import assign_units, scene_cost
 
@@ -309,9 +312,11 @@ def _copy_streams(dev):
 
 
 def render_batches(pipeline, files, batches, args, pipelined=True):
-    """Yield (items, hdr images on the host) per batch, in order.  Pipelined: loader thread -> pinned batch
-    -> side-stream H2D -> render on the current stream -> side-stream D2H into pinned memory; batch i is
-    yielded (and its files written by the caller) while batch i+1 renders and batch i+2 loads."""
+    """Yield (items, hdr images on the host, display frames on the host or None) per batch, in order.  Pipelined:
+    loader thread -> pinned batch -> side-stream H2D -> render on the current stream -> side-stream D2H into pinned
+    memory; batch i is yielded (and its files written by the caller) while batch i+1 renders and batch i+2 loads.
+    The display frames (uint8, pipeline.to_ldr) exist only with a tone mapper or an exposure (infer.device_ldr);
+    without them the caller's PNG is hdr_to_ldr of the host frame."""
     dev = pipeline.device
     # (the pinned D2H slots below take the RETURNED frames' shape: the requested H x W, also under --overscan)
     kw = dict(resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision],
@@ -319,6 +324,8 @@ def render_batches(pipeline, files, batches, args, pipelined=True):
 
     model = getattr(pipeline, "model", None)
     resolve = getattr(pipeline, "resolve", None)
+    want_ldr = device_ldr(args)
+    ldr_kw = (getattr(args, "tone_mapper", "none"), getattr(args, "exposure", 0.0))
 
     def render(batch, host=None):
         if host is not None and hasattr(model, "plan_hint"):  # a new scene's plan from the host mask: no read-back
@@ -335,7 +342,7 @@ def render_batches(pipeline, files, batches, args, pipelined=True):
             imgs = render({k: v.to(dev) for k, v in host.items()}, host)
             if resolve is not None:
                 resolve(imgs)
-            yield items, imgs.cpu()
+            yield items, imgs.cpu(), (pipeline.to_ldr(imgs, *ldr_kw).cpu() if want_ldr else None)
         return
     # HDF5 decode (zlib releases the GIL) runs LOADERS batches ahead on a thread pool, consumed in order
     pool = ThreadPoolExecutor(max_workers=LOADERS, thread_name_prefix="rf_loader", initializer=_one_omp_thread)
@@ -363,6 +370,7 @@ def render_batches(pipeline, files, batches, args, pipelined=True):
     # (items, pinned host images, their copy event, pinned inputs, device images) of the batches in flight: batch i is
     # handed out once batch i + DEPTH is issued, so a late loader or a slow issue does not drain the GPU's queue
     pending = []
+    framed = []  # (items, host images, host display frames, their copy event, device images) resolved, LDR on its way
 
     def upload():
         """The next loaded batch (waiting for the loader if it is late) copied to the device on the H2D stream."""
@@ -411,9 +419,31 @@ def render_batches(pipeline, files, batches, args, pipelined=True):
             # rendered again in place, and copied back again
             if resolve is not None and STAGES.timed("main: range check", resolve, p_imgs):
                 p_out.copy_(p_imgs)
-            t_y = time.perf_counter()
-            yield p_items, p_out
-            STAGES.add("main: consumer (writer submission)", time.perf_counter() - t_y)
+            if not want_ldr:
+                t_y = time.perf_counter()
+                yield p_items, p_out, None
+                STAGES.add("main: consumer (writer submission)", time.perf_counter() - t_y)
+                continue
+            # the display frame of the RESOLVED frame (resolve may have rendered it again in place), made and copied
+            # back on the D2H stream into pinned memory like the HDR frame: a quarter of its bytes.  That stream is
+            # in order behind the copies of the batches issued since, so the batch is not waited for here: it is
+            # handed out, in order, once its display frame has landed (all of them after the last batch)
+            t_l = time.perf_counter()
+            with torch.cuda.stream(d2h):
+                ldr_dev = pipeline.to_ldr(p_imgs, *ldr_kw)
+                p_ldr = torch.empty(ldr_dev.shape, dtype=ldr_dev.dtype, pin_memory=True)
+                p_ldr.copy_(ldr_dev, non_blocking=True)
+                ldr_copied = torch.cuda.Event()
+                ldr_copied.record(d2h)
+            del ldr_dev  # (allocated and used on the D2H stream only)
+            STAGES.add("main: display frame issue", time.perf_counter() - t_l)
+            framed.append((p_items, p_out, p_ldr, ldr_copied, p_imgs))
+            while framed and (nxt is None or framed[0][3].query()):
+                f_items, f_out, f_ldr, f_copied, _ = framed.pop(0)
+                STAGES.timed("main: wait for display frame + D2H", f_copied.synchronize)
+                t_y = time.perf_counter()
+                yield f_items, f_out, f_ldr
+                STAGES.add("main: consumer (writer submission)", time.perf_counter() - t_y)
         if nxt is None:
             return
 
@@ -467,13 +497,14 @@ def main(argv=None, pipeline=None):
     writers = None if inline else ThreadPoolExecutor(max_workers=WRITERS, thread_name_prefix="rf_writer",
                                                     initializer=_one_omp_thread)
     pending = []
-    for items, imgs in render_batches(pipeline, files, batches, args, pipelined=not inline):
+    for items, imgs, ldr in render_batches(pipeline, files, batches, args, pipelined=not inline):
         for i, it in enumerate(items):
             base = os.path.splitext(os.path.basename(it["file_path"]))[0]
+            ldr_i = None if ldr is None else ldr[i]
             if writers is None:
-                save_views(imgs[i], output_dir, base, STAGES)
+                save_views(imgs[i], output_dir, base, STAGES, ldr_i)
             else:  # EXR/PNG encode + write off the render loop (zlib releases the GIL)
-                pending.append(writers.submit(save_views, imgs[i], output_dir, base, STAGES))
+                pending.append(writers.submit(save_views, imgs[i], output_dir, base, STAGES, ldr_i))
             n_frames += imgs.shape[1]
     if writers is not None:
         for f in pending:

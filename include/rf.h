@@ -39,6 +39,8 @@
  *   rf_scene_pos       trans_to_cam_coord (transform.py:7-27) + process_tri_vpos_list (renderformer.py:103-124)
  *   rf_embed           token assembly renderformer.py:139-163, view_transformer.py:108 (RMSNorm eps=None)
  *   rf_hdr_output      ELU(1e-3) (view_transformer.py:86,122) + 10^x - 1 + permute (rendering_pipeline.py:119-123)
+ *   rf_tonemap_ldr8    the display frame of infer.py:94-98: simple_ocio.ToneMapper.hdr_to_ldr (Khronos PBR Neutral only,
+ *                      from its public definition) + sRGB encode + * 255 / astype(uint8)
  *   rf_conv2d_bf16x3   DPT nn.Conv2d (dpt.py:44-52, 69-72, 124-125, 184-192, 208-213, 232-240; aten conv2d) with
  *                      the ResidualConvUnit SiLU/skip (dpt.py:86-92) and fusion sum (:141-143) fused; FINAL mode
  *                      also fuses output_conv2 SiLU + 1x1 (dpt.py:234-240), ELU and the log decode
@@ -80,7 +82,8 @@ extern "C" {
  * that a zero-initialised caller leaves NULL / 0 (= the behaviour before them); nothing that existed changed.
  * Still 16 with rf_ray_tokens_hw / rf_patchify_rays_hw: two new symbols.
  * Still 16 with rf_ray_tokens_cam / rf_hdr_output_win / rf_frame_window: three new symbols.
- * Still 16 with rf_conv_plan_query: a new symbol. */
+ * Still 16 with rf_conv_plan_query: a new symbol.
+ * Still 16 with rf_tonemap_ldr8: a new symbol. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -457,6 +460,23 @@ int rf_hdr_output_win(const float* logits, float* out, int n, int c, int h, int 
 /* The same window of FINISHED channels-last frames f32 [n, h, w, c] -> out [n, oh, ow, c], a copy: the crop of an
  * overscanned frame, whose decode already ran in the epilogue of the DPT's last convolution (RF_CONV_FINAL). */
 int rf_frame_window(const float* frames, float* out, int n, int h, int w, int c, int y0, int x0, int oh, int ow,
+                    void* stream);
+
+/* Linear HDR frames f32 [n_pix, 3] (channels-last, contiguous) -> the 8-bit display frame.  Per pixel c = (r, g, b):
+ *   1. c = max(c * gain, 0) per channel (gain = 2^exposure stops; NaN -> 0, +inf stays +inf);
+ *   2. RF_TONEMAP_NONE: m = c.  RF_TONEMAP_PBR_NEUTRAL (Khronos PBR Neutral): x = min(r, g, b), offset = x < 0.08 ?
+ *      x - 6.25 x^2 : 0.04, c -= offset, peak = max(r, g, b); peak < 0.76: m = c; else with d = 0.24: newPeak = 1 -
+ *      d^2 / (peak + d - 0.76), c *= newPeak / peak, g = 1 - 1 / (0.15 (peak - newPeak) + 1), m = c (1 - g) +
+ *      newPeak g; peak = +inf gives (1, 1, 1);
+ *   3. NONE: v = min(m, 1), no transfer function.  PBR_NEUTRAL: v = srgb(clamp(m, 0, 1)), srgb(t) = t <= 0.0031308 ?
+ *      12.92 t : 1.055 t^(1/2.4) - 0.055, srgb(1) = 1;
+ *   4. q = (uint8)floor(v * 255.0f): one fp32 multiply and a truncation, numpy's (x * 255).astype(uint8).
+ * ldr: u8 [n_pix, 3] (q), mapped: f32 [n_pix, 3] (v); either may be NULL, not both.  hdr and mapped 16-B aligned, ldr
+ * 4-B aligned, gain finite and > 0; n_pix == 0 launches nothing.  Nothing but the n_pix * 3 elements of each given
+ * output is written. */
+#define RF_TONEMAP_NONE 0
+#define RF_TONEMAP_PBR_NEUTRAL 1
+int rf_tonemap_ldr8(const float* hdr, uint8_t* ldr, float* mapped, int64_t n_pix, int mapper, float gain,
                     void* stream);
 
 /* DPT convolutions on the GEMM engine.  Activations are NHWC; a convolution reads its input as two

@@ -2,7 +2,7 @@
 
     python infer.py --h5_file scene.h5 [--model_id DIR|NAME] [--precision bf16|fp16|fp32]
                     [--resolution 512] [--height H] [--width W] [--output_dir DIR]
-                    [--overscan] [--tone_mapper none] [--synthetic_seed S]
+                    [--overscan] [--tone_mapper none|pbr_neutral] [--exposure STOPS] [--synthetic_seed S]
 
 Reads the HDF5 scene with renderformer_amd.h5io (no h5py), renders every view on the HIP
 device and writes `{base}_view_{i}.exr` (linear HDR) and `{base}_view_{i}.png` (clip to
@@ -14,8 +14,9 @@ rectangular frame, e.g. `--height 576 --width 1024`; the scene's fov is the vert
 of view of the frame height.  Each side must be a multiple of the model's frame unit (64 for the
 released Swin models) unless `--overscan` is given, e.g. `--height 1080 --width 1920 --overscan`:
 the padded frame (1088 rows) is rendered as a slightly wider view and the requested window
-written.  Tone mappers other than 'none' need the OCIO configs of `simple_ocio`,
-which is not available here, and are rejected.
+written.  `--tone_mapper pbr_neutral` (Khronos PBR Neutral + sRGB encode) and `--exposure`
+(stops) make the PNG's 8-bit frame on the device (`pipeline.to_ldr`); 'agx' and 'filmic' need
+the OCIO configs of `simple_ocio`, which are not available here, and are rejected.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ import torch
 
 from renderformer_amd import RenderFormerRenderingPipeline
 from renderformer_amd.h5io import load_single_h5_data
-from renderformer_amd.images import hdr_to_ldr, write_exr, write_png
+from renderformer_amd.images import check_tone_mapper, hdr_to_ldr, write_exr, write_png
 
 PRECISION = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}
 
@@ -43,6 +44,8 @@ def add_common_args(parser: argparse.ArgumentParser) -> None:
                         help="Render any frame size (e.g. --height 1080 --width 1920): the frame padded to multiples "
                              "of the model's frame unit is rendered and the requested window returned")
     parser.add_argument("--tone_mapper", type=str, choices=["none", "agx", "filmic", "pbr_neutral"], default="none")
+    parser.add_argument("--exposure", type=float, default=0.0,
+                        help="Exposure of the PNG frames in stops (the frame is scaled by 2^exposure; default 0)")
     parser.add_argument("--synthetic_seed", type=int, default=None,
                         help="(offline) random-init weights of the named architecture")
 
@@ -56,9 +59,10 @@ def frame_resolution(args):
 
 
 def load_pipeline(args) -> RenderFormerRenderingPipeline:
-    if args.tone_mapper != "none":
-        raise SystemExit(f"tone mapper {args.tone_mapper!r} needs simple_ocio's OCIO configs (not available); "
-                         "use --tone_mapper none")
+    try:
+        check_tone_mapper(args.tone_mapper)
+    except ValueError as e:  # agx / filmic: LUT transforms of simple_ocio's OCIO configuration
+        raise SystemExit(str(e))
     model_id = args.model_id
     if args.synthetic_seed is not None and model_id.startswith("microsoft/"):
         model_id = model_id.split("/", 1)[1]
@@ -69,19 +73,32 @@ def load_pipeline(args) -> RenderFormerRenderingPipeline:
     return pipe.to("cuda")
 
 
-def save_views(hdr: torch.Tensor, output_dir: str, base_name: str, stages=None) -> list:
-    """hdr [nv, H, W, 3] -> {base}_view_{i}.exr / .png (infer.py:89-103).  `stages`: batch_infer.StageTimes."""
+def device_ldr(args) -> bool:
+    """Do the parsed flags ask for display frames made on the device (pipeline.to_ldr)?  Not with the defaults
+    (--tone_mapper none --exposure 0): then the PNG is hdr_to_ldr of the host frame, as the reference writes it."""
+    return args.tone_mapper != "none" or getattr(args, "exposure", 0.0) != 0.0
+
+
+def save_views(hdr: torch.Tensor, output_dir: str, base_name: str, stages=None, ldr=None) -> list:
+    """hdr [nv, H, W, 3] -> {base}_view_{i}.exr / .png (infer.py:89-103).  `stages`: batch_infer.StageTimes.
+    `ldr` uint8 [nv, H, W, 3] (tensor or array): the PNG frames, written in place of hdr_to_ldr(hdr[i])."""
     paths = []
     for i in range(hdr.shape[0]):
         img = hdr[i].cpu().numpy().astype("float32")
         hdr_path = os.path.join(output_dir, f"{base_name}_view_{i}.exr")
         ldr_path = os.path.join(output_dir, f"{base_name}_view_{i}.png")
+
+        def to_ldr():
+            if ldr is None:
+                return hdr_to_ldr(img)
+            return ldr[i].cpu().numpy() if isinstance(ldr, torch.Tensor) else ldr[i]
+
         if stages is None:
             write_exr(hdr_path, img)
-            write_png(ldr_path, hdr_to_ldr(img))
+            write_png(ldr_path, to_ldr())
         else:
             stages.timed("write: EXR", write_exr, hdr_path, img)
-            stages.timed("write: PNG", lambda: write_png(ldr_path, hdr_to_ldr(img)))
+            stages.timed("write: PNG", lambda: write_png(ldr_path, to_ldr()))
         paths += [hdr_path, ldr_path]
     return paths
 
@@ -105,11 +122,13 @@ def main(argv=None):
     imgs = pipeline(triangles=triangles, texture=texture, mask=mask, vn=vn, c2w=c2w, fov=fov,
                     resolution=frame_resolution(args), torch_dtype=PRECISION[args.precision], overscan=args.overscan)
     pipeline.resolve(imgs)  # the frame's fp16 range check (re-rendered in place if it overflowed) before reading it
+    # the display frames of a tone mapper / exposure are made on the device, after the frame's resolve
+    ldr = pipeline.to_ldr(imgs, args.tone_mapper, args.exposure).cpu() if device_ldr(args) else None
     print("Inference completed. Rendered images shape:", imgs.shape)
     output_dir = args.output_dir if args.output_dir else os.path.dirname(os.path.abspath(args.h5_file))
     os.makedirs(output_dir, exist_ok=True)
     base = os.path.splitext(os.path.basename(args.h5_file))[0]
-    for p in save_views(imgs[0], output_dir, base):
+    for p in save_views(imgs[0], output_dir, base, ldr=None if ldr is None else ldr[0]):
         print(f"Saved {p}")
     return 0
 

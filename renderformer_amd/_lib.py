@@ -76,6 +76,7 @@ SIGNATURES = {
     "rf_ray_tokens_cam": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "rf_hdr_output_win": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
     "rf_frame_window": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "rf_tonemap_ldr8": [_P, _P, _P, _L, _I, _F, _P],
     "rf_ray_tokens": [_P, _P, _I, _I, _I, _P, _P, _P],
     "rf_patchify_rays": [_P, _I, _I, _I, _P, _P],
     "rf_scene_pos": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _L, _P],

@@ -413,6 +413,106 @@ __global__ __launch_bounds__(256) void frame_window_kernel(const float* __restri
     out[i] = in[((img * h + (y0 + oy)) * w + x0) * c + col];
 }
 
+// ----------------------------------------------------------------------------- display (LDR) frames
+// Linear HDR f32 [n_pix, 3] -> 8-bit display frame (rf.h rf_tonemap_ldr8): c = max(c * gain, 0) (NaN -> 0), the
+// mapper, the display encode v and q = (uint8)(v * 255.0f), one fp32 multiply and a truncation like numpy's
+// (x * 255).astype(uint8).
+// sRGB OETF of t in [0, 1].  t = 1 is returned as 1: fl32(1.055f - 0.055f) is 1 - 2^-24, which times 255 truncates
+// to 254, and white (every value the mappers saturate to 1) must quantise to 255.
+RF_DEV float srgb_encode(float t) {
+    if (t >= 1.0f) return 1.0f;
+    return t <= 0.0031308f ? 12.92f * t : 1.055f * powf(t, 1.0f / 2.4f) - 0.055f;
+}
+
+// Khronos PBR Neutral (the public Khronos tone-mapping specification), from its definition; r, g, b >= 0, +inf allowed
+RF_DEV void pbr_neutral(float& r, float& g, float& b) {
+    const float x = fminf(r, fminf(g, b));
+    const float offset = x < 0.08f ? x - 6.25f * x * x : 0.04f;
+    r -= offset;
+    g -= offset;
+    b -= offset;
+    const float peak = fmaxf(r, fmaxf(g, b));
+    if (peak < 0.76f) return;
+    if (peak > 3.0e38f) {  // +inf (inf / inf below would be NaN): the limit of the curve
+        r = g = b = 1.0f;
+        return;
+    }
+    const float d = 0.24f;
+    const float new_peak = 1.0f - d * d / (peak + d - 0.76f);
+    const float s = new_peak / peak;
+    const float k = 1.0f - 1.0f / (0.15f * (peak - new_peak) + 1.0f);
+    r = r * s * (1.0f - k) + new_peak * k;
+    g = g * s * (1.0f - k) + new_peak * k;
+    b = b * s * (1.0f - k) + new_peak * k;
+}
+
+// one pixel: (r, g, b) in, the display-encoded v in [0, 1] out
+template <int MAPPER>
+RF_DEV void tonemap_pixel(float& r, float& g, float& b, float gain) {
+    r *= gain;
+    g *= gain;
+    b *= gain;
+    r = r > 0.f ? r : 0.f;  // (NaN compares false: 0)
+    g = g > 0.f ? g : 0.f;
+    b = b > 0.f ? b : 0.f;
+    if (MAPPER == RF_TONEMAP_PBR_NEUTRAL) {
+        pbr_neutral(r, g, b);
+        r = srgb_encode(fmaxf(r, 0.f));
+        g = srgb_encode(fmaxf(g, 0.f));
+        b = srgb_encode(fmaxf(b, 0.f));
+    } else {
+        r = fminf(r, 1.0f);
+        g = fminf(g, 1.0f);
+        b = fminf(b, 1.0f);
+    }
+}
+
+RF_DEV unsigned quant8(float v) { return (unsigned)(v * 255.0f); }  // v in [0, 1]: 0 .. 255
+
+// Four pixels per lane: 48 contiguous bytes in as three 16-byte loads, 12 bytes of packed channels out as three
+// 4-byte stores (48 bytes of v as three 16-byte stores), grid-stride over the n_pix / 4 groups; the last n_pix % 4
+// pixels go one per lane through the first lanes of block 0.
+template <int MAPPER>
+__global__ __launch_bounds__(256) void tonemap_ldr8_kernel(const float* __restrict__ hdr, uint8_t* __restrict__ ldr,
+                                                           float* __restrict__ mapped, int64_t n_pix, float gain) {
+    const int64_t n_grp = n_pix >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_grp; i += (int64_t)gridDim.x * blockDim.x) {
+        const float4* src = reinterpret_cast<const float4*>(hdr) + i * 3;
+        float4 a = src[0], b = src[1], c = src[2];  // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        tonemap_pixel<MAPPER>(a.x, a.y, a.z, gain);
+        tonemap_pixel<MAPPER>(a.w, b.x, b.y, gain);
+        tonemap_pixel<MAPPER>(b.z, b.w, c.x, gain);
+        tonemap_pixel<MAPPER>(c.y, c.z, c.w, gain);
+        if (mapped) {
+            float4* dst = reinterpret_cast<float4*>(mapped) + i * 3;
+            dst[0] = a;
+            dst[1] = b;
+            dst[2] = c;
+        }
+        if (ldr) {
+            uint32_t* dst = reinterpret_cast<uint32_t*>(ldr) + i * 3;
+            dst[0] = quant8(a.x) | quant8(a.y) << 8 | quant8(a.z) << 16 | quant8(a.w) << 24;
+            dst[1] = quant8(b.x) | quant8(b.y) << 8 | quant8(b.z) << 16 | quant8(b.w) << 24;
+            dst[2] = quant8(c.x) | quant8(c.y) << 8 | quant8(c.z) << 16 | quant8(c.w) << 24;
+        }
+    }
+    const int64_t p = n_grp * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && p < n_pix) {
+        float r = hdr[p * 3], g = hdr[p * 3 + 1], b = hdr[p * 3 + 2];
+        tonemap_pixel<MAPPER>(r, g, b, gain);
+        if (mapped) {
+            mapped[p * 3] = r;
+            mapped[p * 3 + 1] = g;
+            mapped[p * 3 + 2] = b;
+        }
+        if (ldr) {
+            ldr[p * 3] = (uint8_t)quant8(r);
+            ldr[p * 3 + 1] = (uint8_t)quant8(g);
+            ldr[p * 3 + 2] = (uint8_t)quant8(b);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int rf_texture_pack(float* texture, int64_t n_rows, int channels, int patch_elems, int log_channels,
@@ -639,4 +739,28 @@ extern "C" int rf_frame_window(const float* frames, float* out, int n, int h, in
     RF_LAUNCH(frame_window_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames,
               out, n_elems, h, w, c, y0, x0, oh, ow);
     return rf::check_launch("rf_frame_window");
+}
+
+extern "C" int rf_tonemap_ldr8(const float* hdr, uint8_t* ldr, float* mapped, int64_t n_pix, int mapper, float gain,
+                               void* stream) {
+    RF_REQUIRE(hdr && (ldr || mapped), "rf_tonemap_ldr8: null pointer (hdr, and at least one of ldr and mapped)");
+    RF_REQUIRE(mapper == RF_TONEMAP_NONE || mapper == RF_TONEMAP_PBR_NEUTRAL, "rf_tonemap_ldr8: unknown mapper %d",
+               mapper);
+    RF_REQUIRE(gain > 0.f && gain <= 3.402823466e38f, "rf_tonemap_ldr8: gain must be finite and positive (got %g)",
+               (double)gain);
+    RF_REQUIRE(n_pix >= 0 && n_pix < (1ll << 40), "rf_tonemap_ldr8: need 0 .. 2^40 pixels");
+    RF_REQUIRE(((uintptr_t)hdr & 15) == 0 && ((uintptr_t)mapped & 15) == 0,
+               "rf_tonemap_ldr8: hdr and mapped must be 16-B aligned");
+    RF_REQUIRE(((uintptr_t)ldr & 3) == 0, "rf_tonemap_ldr8: ldr must be 4-B aligned");
+    if (n_pix == 0) return RF_OK;
+    // bandwidth-bound: at most 2,048 blocks (8 per CU), the rest of a large frame by the grid-stride loop
+    const int64_t blocks = (n_pix / 4 + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks));
+    if (mapper == RF_TONEMAP_PBR_NEUTRAL)
+        RF_LAUNCH(tonemap_ldr8_kernel<RF_TONEMAP_PBR_NEUTRAL>, grid, dim3(256), 0, (hipStream_t)stream, hdr, ldr, mapped,
+                  n_pix, gain);
+    else
+        RF_LAUNCH(tonemap_ldr8_kernel<RF_TONEMAP_NONE>, grid, dim3(256), 0, (hipStream_t)stream, hdr, ldr, mapped,
+                  n_pix, gain);
+    return rf::check_launch("rf_tonemap_ldr8");
 }

@@ -138,6 +138,59 @@ def read_png(path: str) -> np.ndarray:
     return raw[:, 1:].reshape(h, w, c)
 
 
-def hdr_to_ldr(hdr: np.ndarray) -> np.ndarray:
-    """`infer.py:94-95` with tone_mapper 'none': clip to [0, 1], scale by 255, truncate to uint8."""
-    return (np.clip(hdr, 0, 1) * 255).astype(np.uint8)
+TONE_MAPPERS = ("none", "pbr_neutral")  # of the reference's --tone_mapper {none, agx, filmic, pbr_neutral}
+
+
+def check_tone_mapper(name: str) -> str:
+    """`name` if it is one of TONE_MAPPERS; ValueError otherwise ('agx' and 'filmic' are LUT transforms of
+    simple_ocio's OCIO configuration, whose files are not available: the text the CLIs exit with)."""
+    if name in TONE_MAPPERS:
+        return name
+    if name in ("agx", "filmic"):
+        raise ValueError(f"tone mapper {name!r} needs simple_ocio's OCIO configs (not available); "
+                         "use --tone_mapper none")
+    raise ValueError(f"unknown tone mapper {name!r}: choose from {TONE_MAPPERS}")
+
+
+def _srgb_encode(t: np.ndarray) -> np.ndarray:
+    """sRGB OETF of float32 t in [0, 1]; srgb(1) = 1 (fl32(1.055 - 0.055) is below 1 and would quantise to 254)."""
+    f = np.float32
+    with np.errstate(invalid="ignore"):
+        hi = f(1.055) * np.power(t, f(1.0 / 2.4), dtype=f) - f(0.055)
+    return np.where(t >= f(1.0), f(1.0), np.where(t <= f(0.0031308), f(12.92) * t, hi)).astype(f)
+
+
+def _pbr_neutral(c: np.ndarray) -> np.ndarray:
+    """Khronos PBR Neutral of float32 c [..., 3] >= 0 (+inf allowed), from the Khronos definition."""
+    f = np.float32
+    x = c.min(axis=-1, keepdims=True)
+    with np.errstate(invalid="ignore", over="ignore"):  # (the unselected toe branch of a huge or infinite minimum)
+        offset = np.where(x < f(0.08), x - f(6.25) * x * x, f(0.04)).astype(f)
+        c = c - offset
+    peak = c.max(axis=-1, keepdims=True)
+    d = f(0.24)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        new_peak = f(1.0) - d * d / (peak + d - f(0.76))
+        k = f(1.0) - f(1.0) / (f(0.15) * (peak - new_peak) + f(1.0))
+        m = c * (new_peak / peak) * (f(1.0) - k) + new_peak * k
+    m = np.where(np.isinf(peak), f(1.0), m)  # the curve's limit, not inf / inf
+    return np.where(peak < f(0.76), c, m).astype(f)
+
+
+def hdr_to_ldr(hdr: np.ndarray, tone_mapper: str = "none", exposure: float = 0.0) -> np.ndarray:
+    """Linear HDR [..., 3] -> uint8 display frame, in float32 numpy: the arithmetic of rf_tonemap_ldr8 (rf.h) for
+    callers without a device.  c = max(hdr * 2^exposure, 0) (NaN -> 0); 'none' (`infer.py:94-95`): clip to [0, 1];
+    'pbr_neutral': Khronos PBR Neutral, then the sRGB encode; then scale by 255 and truncate to uint8.  The default
+    call is the reference's expression itself."""
+    check_tone_mapper(tone_mapper)
+    if tone_mapper == "none" and exposure == 0:
+        return (np.clip(hdr, 0, 1) * 255).astype(np.uint8)
+    f = np.float32
+    c = np.asarray(hdr, dtype=f) * f(2.0 ** float(exposure))
+    with np.errstate(invalid="ignore"):
+        c = np.where(c > 0, c, f(0.0)).astype(f)
+    if tone_mapper == "pbr_neutral":
+        v = _srgb_encode(np.clip(_pbr_neutral(c), f(0.0), f(1.0)))
+    else:
+        v = np.minimum(c, f(1.0))
+    return (v * f(255.0)).astype(np.uint8)

@@ -935,3 +935,33 @@ def frame_window(frames: torch.Tensor, window) -> torch.Tensor:
     out = torch.empty(n, oh, ow, c, dtype=torch.float32, device=frames.device)
     call("rf_frame_window", ptr(frames), ptr(out), n, h, w, c, y0, x0, oh, ow, stream())
     return out
+
+
+TONEMAP = {"none": 0, "pbr_neutral": 1}  # rf.h RF_TONEMAP_*
+
+
+def tonemap_ldr8(hdr: torch.Tensor, mapper: str = "none", exposure: float = 0.0, *, out: torch.Tensor = None,
+                 mapped: bool = False):
+    """The 8-bit display frame of linear HDR frames (rf_tonemap_ldr8): ``hdr`` [..., 3] float32, contiguous, on the
+    device -> uint8 of the same shape; gain ``2 ** exposure`` (stops), ``mapper`` 'none' (clip to [0, 1]) or
+    'pbr_neutral' (Khronos PBR Neutral + sRGB encode), then ``* 255`` and truncation.  ``out``: a uint8 tensor of
+    hdr's shape to write (and return); ``mapped=True`` returns ``(ldr, v)`` with v the float32 display-encoded values
+    before quantisation.  ``hdr`` is only read."""
+    _check(mapper in TONEMAP, f"tonemap_ldr8: unknown mapper {mapper!r}: choose from {tuple(TONEMAP)}")
+    _dev(hdr, torch.float32, "hdr")
+    _check(hdr.dim() >= 1 and hdr.shape[-1] == 3 and hdr.is_contiguous(),
+           f"tonemap_ldr8: hdr must be contiguous [..., 3], got {tuple(hdr.shape)} with strides {hdr.stride()}")
+    _check(-126.0 <= float(exposure) < 128.0,  # (NaN fails too)
+           f"tonemap_ldr8: exposure {exposure} stops does not give a float32 gain")
+    gain = 2.0 ** float(exposure)
+    if out is None:
+        out = torch.empty(hdr.shape, dtype=torch.uint8, device=hdr.device)
+    else:
+        _check(out.dtype == torch.uint8 and out.device == hdr.device and out.shape == hdr.shape
+               and out.is_contiguous(), "tonemap_ldr8: out must be a contiguous uint8 tensor of hdr's shape on its "
+               "device")
+    v = torch.empty_like(hdr) if mapped else None
+    if hdr.numel() > 0:  # (an empty tensor has no pointer to hand over)
+        call("rf_tonemap_ldr8", ptr(hdr), ptr(out), ptr(v), hdr.numel() // 3, TONEMAP[mapper], gain,
+             stream())
+    return (out, v) if mapped else out

@@ -135,6 +135,30 @@ class RenderFormerRenderingPipeline:
         self.last_precision = {"requested": str(torch_dtype), "computed": self.model.precision}
         return out
 
+    def to_ldr(self, hdr: torch.Tensor, tone_mapper: str = "none", exposure: float = 0.0, out: torch.Tensor = None):
+        """The 8-bit display frame of rendered HDR frames, made on the device (one HIP kernel, ``ops.tonemap_ldr8``):
+        ``hdr`` [bs, nv, H, W, 3] (or any contiguous [..., 3]) float32 on the device -> ``torch.uint8`` of the same
+        shape on the same device, a quarter of the bytes to copy to the host.  ``hdr`` is only read.
+
+        ``tone_mapper`` takes the reference CLI's names: ``"none"`` clips to [0, 1] (what the reference's
+        ``infer.py`` writes without a tone mapper: no transfer function); ``"pbr_neutral"`` is Khronos PBR Neutral,
+        written from the Khronos definition, followed by the sRGB encode.  ``"agx"`` and ``"filmic"`` are LUT
+        transforms of ``simple_ocio``'s OCIO configuration, whose data is not available: ValueError.  ``exposure``
+        (stops) scales the frame by ``2 ** exposure`` first.  Then ``* 255`` and truncation, like numpy's
+        ``(x * 255).astype(uint8)``; NaN and negative values give 0, +inf gives 255.  ``out``: a uint8 tensor of
+        hdr's shape to reuse.  ``images.hdr_to_ldr`` is the same arithmetic in numpy.
+
+        With ``range_check="lazy"`` call ``to_ldr`` AFTER ``resolve(out)``: ``resolve`` may render the HDR frame
+        again in place, and a display frame made before it would show the overflowed one.  The default ``"sync"``
+        mode has resolved the frame when ``render`` returns, so there is no such order."""
+        from . import ops
+        from .images import check_tone_mapper
+        check_tone_mapper(tone_mapper)
+        if not isinstance(hdr, torch.Tensor) or not hdr.is_cuda:
+            raise ValueError("to_ldr: hdr must be a tensor on the HIP device (images.hdr_to_ldr is the numpy form)")
+        with torch.cuda.device(hdr.device):
+            return ops.tonemap_ldr8(hdr, tone_mapper, exposure, out=out)
+
     def resolve(self, out=None) -> bool:
         """RenderFormer.resolve: finish the fp16 range check of the frame ``out`` (every pending frame if None),
         waiting for it; an overflowed frame is rendered again in place.  Only needed with range_check="lazy" (the
