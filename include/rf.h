@@ -41,6 +41,10 @@
  *   rf_hdr_output      ELU(1e-3) (view_transformer.py:86,122) + 10^x - 1 + permute (rendering_pipeline.py:119-123)
  *   rf_tonemap_ldr8    the display frame of infer.py:94-98: simple_ocio.ToneMapper.hdr_to_ldr (Khronos PBR Neutral only,
  *                      from its public definition) + sRGB encode + * 255 / astype(uint8)
+ *   rf_primary_hits / rf_gbuffer_shade  stand beside RayGenerator (utils/ray_generator.py:13-50), whose rays they
+ *                      trace: nearest hit of every pixel's ray with the scene's triangles (depth, triangle id,
+ *                      barycentrics, alpha) and the hit's shading normal and diffuse albedo.  The reference has no
+ *                      counterpart (its frames are radiance only); the rays are rf_ray_tokens_cam's
  *   rf_conv2d_bf16x3   DPT nn.Conv2d (dpt.py:44-52, 69-72, 124-125, 184-192, 208-213, 232-240; aten conv2d) with
  *                      the ResidualConvUnit SiLU/skip (dpt.py:86-92) and fusion sum (:141-143) fused; FINAL mode
  *                      also fuses output_conv2 SiLU + 1x1 (dpt.py:234-240), ELU and the log decode
@@ -83,7 +87,8 @@ extern "C" {
  * Still 16 with rf_ray_tokens_hw / rf_patchify_rays_hw: two new symbols.
  * Still 16 with rf_ray_tokens_cam / rf_hdr_output_win / rf_frame_window: three new symbols.
  * Still 16 with rf_conv_plan_query: a new symbol.
- * Still 16 with rf_tonemap_ldr8: a new symbol. */
+ * Still 16 with rf_tonemap_ldr8: a new symbol.
+ * Still 16 with rf_primary_hits / rf_gbuffer_shade: two new symbols. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -478,6 +483,54 @@ int rf_frame_window(const float* frames, float* out, int n, int h, int w, int c,
 #define RF_TONEMAP_PBR_NEUTRAL 1
 int rf_tonemap_ldr8(const float* hdr, uint8_t* ldr, float* mapped, int64_t n_pix, int mapper, float gain,
                     void* stream);
+
+/* Primary visibility: for every scene b, view v and pixel (x, y) of a frame_h x frame_w frame, the nearest
+ * intersection of the pixel's ray with the scene's valid triangles (a brute-force pass over every ray / triangle pair).
+ * Inputs as rf_scene_pos: tris f32 [n_scenes * n_tris_per_scene, 9]; valid_idx int32 [n_valid] rows into tris,
+ * grouped by scene with offsets scene_off[n_scenes + 1] (scene_off[n_scenes] = n_valid); rows outside valid_idx are
+ * never read.  c2w f32 [n_scenes * n_views, 4, 4]; the camera is fov_deg [n_scenes * n_views] or intr [n_scenes *
+ * n_views, 4] = (fx, fy, cx, cy), exactly one non-NULL, with rf_ray_tokens_cam's conventions.
+ * Ray: origin = the translation column of c2w; direction = rf_ray_tokens_cam's of pixel (x, y) of the requested frame
+ * (y0 = x0 = 0), the same fp32 expressions: ((x + 0.5 - cx) / fx, -(y + 0.5 - cy) / fy, -1) rotated by c2w and divided by
+ * fmaxf(norm, 1e-12f).  So a pixel here is the ray of the same pixel of a frame rendered with or without overscan.
+ * Hit rule: triangles are double-sided; triangle k is hit iff its plane is not parallel to the ray, the barycentrics
+ * satisfy u >= 0, v >= 0, u + v <= 1 and t > 0; the nearest hit is the smallest t and among equal t the smallest index
+ * wins (deterministic: records are walked in index order with a strict <).  A zero-area triangle (the fp64 cross
+ * product of its edge vectors is zero) or one with a non-finite coordinate is never hit.
+ * Watertight: the inside test uses edge functions d . (p x q) of the origin-relative vertices, each edge's cross
+ * product taken with its vertices in a canonical order and evaluated again in fp64 when within 2.5e-6 |p| |q| of
+ * zero, so two triangles that share an edge (the same two positions bit for bit, any order or winding) never both
+ * reject a ray between them, nor do the triangles round a shared vertex.  t, u, v of a covered pixel come from
+ * Moeller-Trumbore on the input coordinates' edge vectors in fp32; on an edge u or v may be a rounding error below 0.
+ * Outputs, [n_scenes, n_views, frame_h, frame_w] each: depth f32 = t along the normalised ray, +inf on a miss;
+ * tri_id int32 = the hit triangle's index on the n_tris_per_scene axis of its scene (valid_idx - b * n_tris_per_scene,
+ * not the compacted index), -1 on a miss; bary f32 [..., 2] = (u, v), weight u on vertex 1, v on vertex 2, 1 - u - v on
+ * vertex 0, zeros on a miss (may be NULL); alpha u8 = 255 on a hit, 0 on a miss (may be NULL).
+ * work: 32 * n_views * n_valid floats of caller workspace, 16-B aligned (per scene, view and valid triangle: three
+ * edge normals, the threshold and the id, 12 floats the trace reads per pair, and 20 that only the fp64 path and a
+ * covered pair read); written by a setup launch, read by the trace launch that follows it on the same stream.
+ * Limits: frame_h * frame_w < 2^31, n_views <= 65535, n_scenes <= 65535, n_scenes * n_tris_per_scene < 2^31.  A
+ * workgroup traces an RF_VIS_TILE x RF_VIS_TILE pixel tile and stages RF_VIS_CHUNK records at a time in LDS. */
+#define RF_VIS_TILE 16
+#define RF_VIS_CHUNK 256
+int rf_primary_hits(const float* tris, const int32_t* valid_idx, const int32_t* scene_off, const float* c2w,
+                    const float* fov_deg, const float* intr, int n_scenes, int n_views, int n_tris_per_scene,
+                    int64_t n_valid, int frame_h, int frame_w, float* depth, int32_t* tri_id, float* bary,
+                    uint8_t* alpha, float* work, int64_t work_floats, void* stream);
+/* G-buffer shading, elementwise over the n_scenes * pix_per_scene pixels of rf_primary_hits' outputs (pix_per_scene =
+ * n_views * frame_h * frame_w): alpha u8 = 255 where tri_id >= 0, else 0; normal f32 [..., 3] = the world-space
+ * shading normal normalize((1 - u - v) vn0 + u vn1 + v vn2) of vn f32 [n_scenes * n_tris_per_scene, 9], divided by
+ * fmaxf(norm, 1e-12f) and not flipped toward the camera; albedo f32 [..., 3] = channels 0..2 (diffuse) of the hit
+ * triangle's texture at texel (0, 0): texture[row * tex_row_stride + c * tex_chan_stride] with row = b *
+ * n_tris_per_scene + tri_id, which serves both layouts, [*, C, 32, 32] (strides C * 1024, 1024) and [*, C] (C, 1).
+ * Texel (0, 0) is exact for every texture scene_processor/to_h5.py:41-66 writes (constant over the patch mask, the layout
+ * rf_texture_scan proves); a lookup by barycentrics into spatially varying patches is not done.  The diffuse channels
+ * are not log-encoded by rf_texture_pack, so a texture before or after it gives the same albedo.  Misses (and ids
+ * outside 0 .. n_tris_per_scene - 1, which read nothing) give zeros.  Each output may be NULL, not all; normal needs
+ * bary and vn, albedo needs texture.  Nothing is written to the inputs. */
+int rf_gbuffer_shade(const int32_t* tri_id, const float* bary, const float* vn, const float* texture,
+                     int64_t tex_row_stride, int64_t tex_chan_stride, int n_tris_per_scene, int n_scenes,
+                     int64_t pix_per_scene, uint8_t* alpha, float* normal, float* albedo, void* stream);
 
 /* DPT convolutions on the GEMM engine.  Activations are NHWC; a convolution reads its input as two
  * bf16 planes (hi = bf16(x), lo = bf16(x - hi); channel stride cin_pad, padded channels zero) and its

@@ -46,6 +46,10 @@ def add_common_args(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--tone_mapper", type=str, choices=["none", "agx", "filmic", "pbr_neutral"], default="none")
     parser.add_argument("--exposure", type=float, default=0.0,
                         help="Exposure of the PNG frames in stops (the frame is scaled by 2^exposure; default 0)")
+    parser.add_argument("--save_gbuffer", action="store_true",
+                        help="Also write each view's geometry buffers (pipeline.gbuffer): <name>_alpha.png, "
+                             "<name>_depth.exr (one channel, +inf where nothing is hit), <name>_normal.exr, "
+                             "<name>_albedo.exr")
     parser.add_argument("--synthetic_seed", type=int, default=None,
                         help="(offline) random-init weights of the named architecture")
 
@@ -103,6 +107,25 @@ def save_views(hdr: torch.Tensor, output_dir: str, base_name: str, stages=None, 
     return paths
 
 
+def save_gbuffer(gb, output_dir: str, base_name: str) -> list:
+    """One scene's GBuffer fields ([nv, H, W(, 3)], tensors or arrays) -> {base}_view_{i}_alpha.png, _depth.exr (one
+    channel, misses +inf), _normal.exr, _albedo.exr, beside save_views' files."""
+    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t  # noqa: E731
+    alpha, depth, normal, albedo = host(gb.alpha), host(gb.depth), host(gb.normal), host(gb.albedo)
+    paths = []
+    for i in range(depth.shape[0]):
+        stem = os.path.join(output_dir, f"{base_name}_view_{i}")
+        write_png(stem + "_alpha.png", alpha[i])
+        write_exr(stem + "_depth.exr", depth[i])
+        write_exr(stem + "_normal.exr", normal[i])
+        write_exr(stem + "_albedo.exr", albedo[i])
+        paths += [stem + "_alpha.png", stem + "_depth.exr", stem + "_normal.exr", stem + "_albedo.exr"]
+    return paths
+
+
+GBUFFER_FILES = ("alpha", "depth", "normal", "albedo")  # (the triangle id has no image file)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Infer using triangle radiosity transformer model (MI355X)")
     parser.add_argument("--h5_file", type=str, required=True, help="Path to the input H5 file")
@@ -130,6 +153,11 @@ def main(argv=None):
     base = os.path.splitext(os.path.basename(args.h5_file))[0]
     for p in save_views(imgs[0], output_dir, base, ldr=None if ldr is None else ldr[0]):
         print(f"Saved {p}")
+    if args.save_gbuffer:
+        gb = pipeline.gbuffer(triangles, texture, mask, vn, c2w, fov, frame_resolution(args), overscan=args.overscan,
+                              outputs=GBUFFER_FILES)
+        for p in save_gbuffer(type(gb)(*(None if t is None else t[0] for t in gb)), output_dir, base):
+            print(f"Saved {p}")
     return 0
 
 

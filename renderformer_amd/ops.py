@@ -965,3 +965,118 @@ def tonemap_ldr8(hdr: torch.Tensor, mapper: str = "none", exposure: float = 0.0,
         call("rf_tonemap_ldr8", ptr(hdr), ptr(out), ptr(v), hdr.numel() // 3, TONEMAP[mapper], gain,
              stream())
     return (out, v) if mapped else out
+
+
+VIS_TILE = 16    # rf.h RF_VIS_TILE: a workgroup of rf_primary_hits traces a VIS_TILE x VIS_TILE pixel tile
+VIS_CHUNK = 256  # rf.h RF_VIS_CHUNK: the triangle records it stages in LDS per round
+VIS_RECORD_FLOATS = 32  # workspace floats per (view, valid triangle)
+
+
+def primary_hits(tris: torch.Tensor, valid_idx: torch.Tensor, scene_off: torch.Tensor, n_valid: int,
+                 c2w: torch.Tensor, fov_deg: Optional[torch.Tensor], intrinsics: Optional[torch.Tensor], frame, *,
+                 bary: bool = True, alpha: bool = False, out: Optional[dict] = None) -> dict:
+    """Nearest hit of every pixel's primary ray with the valid triangles (rf_primary_hits).  ``tris`` f32 [B, N, 9],
+    ``valid_idx`` int32 [n_valid] rows into its [B N, 9] view grouped by scene, ``scene_off`` int32 [B + 1] (its
+    last entry is ``n_valid``, which the caller knows from the host mask), ``c2w`` f32 [B, V, 4, 4], the camera
+    ``fov_deg`` [B, V] or ``intrinsics`` [B, V, 4] (exactly one), ``frame`` = H or (H, W) as in ``ray_tokens_cam``.
+    Returns {'depth': f32 [B, V, H, W], 'tri_id': int32 [B, V, H, W]} plus 'bary' f32 [B, V, H, W, 2] and 'alpha'
+    uint8 [B, V, H, W] when asked.  ``out``: contiguous tensors to write under those names.  Inputs are only read."""
+    _dev(tris, torch.float32, "tris")
+    _check(tris.dim() == 3 and tris.shape[-1] == 9 and tris.is_contiguous() and tris.shape[1] > 0,
+           f"primary_hits: tris must be contiguous [B, N, 9] with N > 0, got {tuple(tris.shape)}")
+    B, N = tris.shape[:2]
+    _dev(c2w, torch.float32, "c2w")
+    _check(c2w.dim() == 4 and tuple(c2w.shape[2:]) == (4, 4) and c2w.shape[0] == B and c2w.is_contiguous(),
+           f"primary_hits: c2w must be contiguous [{B}, V, 4, 4], got {tuple(c2w.shape)}")
+    V = c2w.shape[1]
+    _check((fov_deg is None) != (intrinsics is None), "primary_hits: exactly one of fov_deg and intrinsics")
+    if fov_deg is not None:
+        _dev(fov_deg, torch.float32, "fov_deg")
+        _check(fov_deg.is_contiguous() and fov_deg.numel() == B * V, "primary_hits: one contiguous fov per camera")
+    else:
+        _dev(intrinsics, torch.float32, "intrinsics")
+        _check(intrinsics.is_contiguous() and intrinsics.numel() == 4 * B * V and intrinsics.shape[-1] == 4,
+               "primary_hits: intrinsics must be contiguous [B, V, 4]: (fx, fy, cx, cy) per camera")
+    n_valid = int(n_valid)
+    for t, n, name in ((valid_idx, n_valid, "valid_idx"), (scene_off, B + 1, "scene_off")):
+        _check(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n,
+               f"primary_hits: {name} must be a contiguous int32 device tensor of {n} entries")
+    h, w = frame_hw(frame)
+    shapes = {"depth": ((B, V, h, w), torch.float32), "tri_id": ((B, V, h, w), torch.int32)}
+    if bary:
+        shapes["bary"] = ((B, V, h, w, 2), torch.float32)
+    if alpha:
+        shapes["alpha"] = ((B, V, h, w), torch.uint8)
+    res = {}
+    for name, (shape, dtype) in shapes.items():
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty([max(s, 0) for s in shape], dtype=dtype, device=tris.device)
+        _check(t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+               f"primary_hits: out[{name!r}] must be a contiguous {dtype} device tensor {shape}")
+        res[name] = t
+    work = torch.empty(max(VIS_RECORD_FLOATS * V * n_valid, 4), dtype=torch.float32, device=tris.device)
+    call("rf_primary_hits", ptr(tris), ptr(valid_idx), ptr(scene_off), ptr(c2w), ptr(fov_deg), ptr(intrinsics), B, V,
+         N, n_valid, h, w, ptr(res["depth"]), ptr(res["tri_id"]), ptr(res.get("bary")), ptr(res.get("alpha")),
+         ptr(work), work.numel(), stream())
+    return res
+
+
+def gbuffer_shade(tri_id: torch.Tensor, bary: Optional[torch.Tensor] = None, vn: Optional[torch.Tensor] = None,
+                  texture: Optional[torch.Tensor] = None, *, alpha: bool = False, normal: bool = False,
+                  albedo: bool = False, out: Optional[dict] = None) -> dict:
+    """(tri_id, bary) -> display buffers (rf_gbuffer_shade).  ``tri_id`` int32 [B, ...] (the scene is its first
+    axis), ``bary`` f32 [B, ..., 2], ``vn`` f32 [B, N, 9] (for 'normal'), ``texture`` f32 [B, N, C, 32, 32] or
+    [B, N, C] with C >= 3 (for 'albedo': texel (0, 0) of channels 0..2).  Returns the buffers asked for: 'alpha' uint8
+    [B, ...], 'normal' and 'albedo' f32 [B, ..., 3].  ``out``: contiguous tensors to write.  Inputs are only read."""
+    _check(alpha or normal or albedo, "gbuffer_shade: ask for at least one of alpha, normal and albedo")
+    _check(tri_id.is_cuda and tri_id.dtype == torch.int32 and tri_id.dim() >= 2 and tri_id.is_contiguous(),
+           "gbuffer_shade: tri_id must be a contiguous int32 device tensor [B, ...]")
+    B = tri_id.shape[0]
+    n_per = None
+    if normal:
+        _check(bary is not None and vn is not None, "gbuffer_shade: normal needs bary and vn")
+        _dev(bary, torch.float32, "bary")
+        _check(tuple(bary.shape) == tuple(tri_id.shape) + (2,) and bary.is_contiguous(),
+               f"gbuffer_shade: bary must be contiguous {tuple(tri_id.shape) + (2,)}, got {tuple(bary.shape)}")
+        _dev(vn, torch.float32, "vn")
+        _check(vn.dim() == 3 and vn.shape[0] == B and vn.shape[2] == 9 and vn.is_contiguous(),
+               f"gbuffer_shade: vn must be contiguous [{B}, N, 9], got {tuple(vn.shape)}")
+        n_per = vn.shape[1]
+    row = chan = 0
+    if albedo:
+        _check(texture is not None, "gbuffer_shade: albedo needs texture")
+        _dev(texture, torch.float32, "texture")
+        _check(texture.dim() in (3, 5) and texture.shape[0] == B and texture.shape[2] >= 3
+               and (n_per is None or texture.shape[1] == n_per),
+               f"gbuffer_shade: texture must be [{B}, N, C >= 3] or [{B}, N, C >= 3, p, p] with vn's N, got "
+               f"{tuple(texture.shape)}")
+        n_per = texture.shape[1]
+        _check(texture.stride(2) >= 1 and texture.stride(1) > 2 * texture.stride(2)
+               and (B == 1 or texture.stride(0) == n_per * texture.stride(1)),
+               f"gbuffer_shade: texture rows must be evenly spaced over [B, N] (strides {texture.stride()})")
+        row, chan = texture.stride(1), texture.stride(2)
+    if n_per is None:  # alpha alone reads no per-triangle row: every id >= 0 is a hit
+        n_per = (2 ** 31 - 1) // max(B, 1)
+    _check(n_per > 0, "gbuffer_shade: scenes without triangles")
+    pix = tri_id.numel() // B if B else 0
+    shapes = {}
+    if alpha:
+        shapes["alpha"] = (tuple(tri_id.shape), torch.uint8)
+    if normal:
+        shapes["normal"] = (tuple(tri_id.shape) + (3,), torch.float32)
+    if albedo:
+        shapes["albedo"] = (tuple(tri_id.shape) + (3,), torch.float32)
+    res = {}
+    for name, (shape, dtype) in shapes.items():
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=tri_id.device)
+        _check(t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+               f"gbuffer_shade: out[{name!r}] must be a contiguous {dtype} device tensor {shape}")
+        res[name] = t
+    if tri_id.numel() > 0:  # (an empty tensor has no pointer to hand over)
+        call("rf_gbuffer_shade", ptr(tri_id), ptr(bary) if normal else 0, ptr(vn) if normal else 0,
+             ptr(texture) if albedo else 0, row, chan, n_per, B, pix, ptr(res.get("alpha")), ptr(res.get("normal")),
+             ptr(res.get("albedo")), stream())
+    return res

@@ -159,6 +159,77 @@ class RenderFormerRenderingPipeline:
         with torch.cuda.device(hdr.device):
             return ops.tonemap_ldr8(hdr, tone_mapper, exposure, out=out)
 
+    def _unit(self) -> int:
+        """The smallest frame side a plan takes: the valid-triangle tables do not depend on views or resolution."""
+        from .model import SWIN_WINDOW
+        return self.config.patch_size * (SWIN_WINDOW if self.config.view_transformer_use_swin_attn else 1)
+
+    def gbuffer(self, triangles, texture, mask, vn, c2w, fov, resolution: Union[int, Tuple[int, int]] = 512, *,
+                intrinsics=None, overscan: bool = False, outputs=None):
+        """Geometry buffers of the frames ``render`` would render from the same arguments: a ``GBuffer`` (``alpha``
+        uint8, ``depth`` float32, ``tri_id`` int32, each [bs, nv, H, W]; ``normal`` and ``albedo`` float32 [bs, nv,
+        H, W, 3]) on the device, from one brute-force visibility pass over the primary rays and the input triangles
+        (``renderformer_amd.gbuffer``: two HIP kernels, no model weights).
+
+        Same argument order, camera conventions (``fov`` or ``intrinsics``) and acceptance rule as ``render``: a
+        call is valid iff the same ``render`` call is, so a side that is no multiple of the frame unit needs
+        ``overscan=True``.  That flag only relaxes the check here: a G-buffer pixel (x, y) is the ray of pixel
+        (x, y) of the requested frame, which is the ray ``render`` traces for it with or without overscan, so the
+        padded frame is never needed.
+
+        ``depth`` is the distance along the normalised ray, +inf where nothing is hit (z-depth: ``t / |d_cam|``);
+        ``tri_id`` indexes the N axis of ``triangles[b]`` (-1: no hit); ``normal`` is the world-space shading normal
+        interpolated from ``vn``, not flipped toward the camera; ``albedo`` is the diffuse colour of the hit
+        triangle, texel (0, 0) of channels 0..2 of its texture (textures that vary over a triangle's patch are not
+        sampled).  Composite over a backplate with ``rgb * a + backplate * (1 - a)``, ``a = alpha / 255``.
+
+        ``texture`` is only READ here -- unlike ``render`` it is NOT log-encoded in place; the diffuse channels are
+        not among the log-encoded ones, so a texture gives the same albedo before and after a ``render``.
+        ``outputs``: a subset of ``("alpha", "depth", "tri_id", "normal", "albedo")`` (None = all); a buffer that is
+        not asked for is not computed (its field is None)."""
+        from . import gbuffer as gb
+        from .model import _check_camera, frame_layout
+        H, W = frame_layout(self.config, resolution, overscan)[:2]
+        _check_camera(c2w, fov, intrinsics)
+        names = gb.check_outputs(outputs)
+        cam = fov if intrinsics is None else intrinsics
+        for t, n in ((triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn"), (c2w, "c2w"),
+                     (cam, "fov" if intrinsics is None else "intrinsics")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"gbuffer: {n} must be a tensor on the HIP device")
+        dev = c2w.device
+        with torch.cuda.device(dev):
+            if self.model._w is not None and self.model.device == dev:
+                plan = self.model._plan(mask, 1, self._unit())  # (cached per mask: no read-back the next time)
+                tables = (plan.valid_flat, plan.scene_off, plan.T_tri)
+            else:
+                tables = gb.scene_tables(mask.cpu().numpy(), dev)
+            return gb.trace(triangles, texture, vn, tables, c2w, fov, intrinsics, (H, W), names)
+
+    def gbuffer_encoded(self, scene, c2w, fov, resolution: Union[int, Tuple[int, int]] = 512, *, intrinsics=None,
+                        overscan: bool = False, outputs=None):
+        """``gbuffer`` of the cameras ``c2w`` / ``fov`` (or ``intrinsics``) for an encoded batch, from the inputs the
+        handle retains (their texture is log-encoded by ``encode``, which leaves the diffuse channels as they
+        were): the same buffers, bit for bit, as ``gbuffer`` of the scene's inputs."""
+        from . import gbuffer as gb
+        from .model import EncodedScene, _check_camera, frame_layout
+        H, W = frame_layout(self.config, resolution, overscan)[:2]
+        _check_camera(c2w, fov, intrinsics)
+        names = gb.check_outputs(outputs)
+        if not isinstance(scene, EncodedScene):
+            raise ValueError(f"gbuffer_encoded needs an EncodedScene (pipeline.encode), got {type(scene)}")
+        cam = fov if intrinsics is None else intrinsics
+        for t, n in ((c2w, "c2w"), (cam, "fov" if intrinsics is None else "intrinsics")):
+            if not isinstance(t, torch.Tensor) or t.device != scene.device:
+                raise ValueError(f"gbuffer_encoded: {n} must be a tensor on {scene.device}")
+        if c2w.shape[0] != scene.batch_size:
+            raise ValueError(f"c2w has batch size {c2w.shape[0]}, the encoded scene {scene.batch_size}")
+        triangles, texture, _, vn = scene.inputs
+        with torch.cuda.device(scene.device):
+            plan = scene.model._plan_host(scene.mask_host, 1, self._unit())  # (the plan encode built)
+            return gb.trace(triangles, texture, vn, (plan.valid_flat, plan.scene_off, plan.T_tri), c2w, fov,
+                            intrinsics, (H, W), names)
+
     def resolve(self, out=None) -> bool:
         """RenderFormer.resolve: finish the fp16 range check of the frame ``out`` (every pending frame if None),
         waiting for it; an overflowed frame is rendered again in place.  Only needed with range_check="lazy" (the
