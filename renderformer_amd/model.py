@@ -21,11 +21,11 @@ The default ("sync") resolves a frame before ``render`` returns by waiting on th
 event only (no device sync, like the caller's own ``.cpu()``), so a caller that never calls
 ``resolve`` — the reference README example, its ``infer.py`` — always reads the final frame.
 Callers that pipeline frames opt in to "lazy" (read at a later render, ``resolve(out)`` or
-``check_range()``: ``batch_infer.py``, ``infer.py``) or "deferred" (``bench.py``).
+``check_range()``: ``batch_infer.py``, ``infer.py``) or "deferred" (``bench.py``).  The range words, the pending
+frames and the three modes are ``range_guard.RangeGuard``'s (``_guard``); changing operands (``_fall_back``) stays here.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 import threading
@@ -39,6 +39,7 @@ from ._lib import load as _load_lib
 from .config import RenderFormerConfig, named_config
 from .dpt import PRECISIONS as DPT_PRECISIONS
 from .dpt import DPTHead
+from .range_guard import RangeGuard, deferred_error
 from .weights import check_state_dict, load_snapshot, synthetic_state_dict
 
 EPS = 1e-6  # layers/attention.py:16
@@ -344,19 +345,6 @@ class PrecisionWarning(UserWarning):
 
 
 RANGE_CHECKS = ("lazy", "sync", "deferred", "off")
-RANGE_WORDS_MAX = 8  # frames with an unresolved range word per model; the oldest is resolved (waited for) beyond
-
-
-class _Frame:
-    """A rendered frame whose fp16 range word is not yet read: the word, the frame's end event and stream, the
-    output tensor, a replay closure (the same render with the texture already log-encoded) and the inputs'
-    version counters (an input edited in place since the render cannot be replayed)."""
-    __slots__ = ("word", "event", "stream", "out", "replay", "inputs", "versions")
-
-    def __init__(self, word, event, stream, out, replay, inputs):
-        self.word, self.event, self.stream, self.out, self.replay = word, event, stream, out, replay
-        self.inputs = inputs
-        self.versions = [t._version for t in inputs]
 
 
 class EncodedScene:
@@ -434,9 +422,7 @@ class RenderFormer:
         if self.range_check not in RANGE_CHECKS:
             raise ValueError(f"range_check must be one of {RANGE_CHECKS}")
         self.range_fallbacks = 0  # frames rendered again with bf16 operands after an fp16 overflow
-        self._range_free: List[int] = []  # range-word handles not in use
-        self._range_pending: List[_Frame] = []  # frames whose word is unread, oldest first
-        self._range_lock = threading.RLock()
+        self._guard = RangeGuard(self)  # the words, the frames whose word is unread, and the lock of both lists
         # render_views: stage 2 + DPT over at most view_chunk views per pass (stage 1 once per scene); None = all
         # views of the batch in one pass.  A fixed chunk makes each view's image independent of the batching.
         self.view_chunk = view_chunk if view_chunk is not None else (int(os.environ.get("RF_VIEW_CHUNK", "0")) or None)
@@ -563,13 +549,7 @@ class RenderFormer:
         last = self._last_plan.get(ko)
         if last is not None and last[0] is mask and last[1] == mask._version:
             return last[2]
-        hint = self._host_masks.get(id(mask))
-        if hint is not None and hint[0] is mask and hint[1] == mask._version:
-            import numpy as np
-            host = np.asarray(hint[2], dtype=bool)
-        else:
-            host = mask.cpu().numpy().astype(bool)  # (device-only mask: one read-back, like unpad_input)
-        plan = self._plan_host(host, V, res)
+        plan = self._plan_host(self._mask_host(mask), V, res)  # (device-only mask: one read-back, like unpad_input)
         if len(self._last_plan) > 128:
             self._last_plan.clear()
         self._last_plan[ko] = (mask, mask._version, plan)
@@ -932,7 +912,7 @@ class RenderFormer:
         cam = dict(intrinsics=intrinsics, overscan=overscan)
         with torch.cuda.device(self._device):
             # the replay (an fp16 overflow's re-render) must not log-encode the texture a second time
-            return self._guarded(
+            return self._guard.run(
                 lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, layout[:2], log_encode, **cam),
                 lambda: self._render_views(triangles, texture, mask, vn, c2w, fov, layout[:2], False, **cam),
                 (triangles, texture, mask, vn, c2w, fov if intrinsics is None else intrinsics))
@@ -949,31 +929,23 @@ class RenderFormer:
         for its end event before returning (once per scene).  An overflow raises DeviceError in the "deferred" mode;
         "sync" / "lazy" move the model to bf16 operands (PrecisionWarning) and encode again."""
         self._require()
-        dev = self._device
-        with torch.cuda.device(dev):
-            for t, n in ((triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn")):
-                if t.device != dev:
-                    raise ValueError(f"{n} must be on {dev} (got {t.device})")
-            sc = EncodedScene(self, self._generation, dev, self._mask_host(mask), (triangles, texture, mask, vn))
+        with torch.cuda.device(self._device):
+            self._on_device([(triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn")])
+            sc = EncodedScene(self, self._generation, self._device, self._mask_host(mask),
+                              (triangles, texture, mask, vn))
             with sc.lock:
                 self._encode_checked(sc, log_encode)
             return sc
 
     def _encode(self, sc: EncodedScene, log_encode: bool):
         """Fill the handle from its inputs with the model's present weights, on the current stream."""
-        cfg, dev = self.config, self._device
+        cfg = self.config
         triangles, texture, _, vn = sc.inputs
-        B = sc.batch_size
         # (stage 1's tables do not depend on the view count or the resolution: the smallest valid plan)
         res0 = cfg.patch_size * (SWIN_WINDOW if cfg.view_transformer_use_swin_attn else 1)
         plan = self._plan_host(sc.mask_host, 1, res0)
         W = self._w
-        tris = triangles.reshape(B, -1, 9).float().contiguous()
-        x1 = self._embed_triangles(plan, texture, vn.reshape(B, -1, 9).float().contiguous(), log_encode)
-        pos1 = torch.empty(plan.T1, 9, dtype=torch.float32, device=dev)
-        ops.scene_pos(tris, plan.valid_flat, plan.scene_off, None, B, 1, cfg.num_register_tokens, pos1, plan.cu1,
-                      max(plan.counts))
-        x1 = self._stage1(plan, x1, pos1)
+        tris, x1 = self._scene_front(plan, triangles, texture, vn, log_encode)
         kv_all = None
         if self._kv_batch(plan.T1) and not self.fp8 and plan.T1 > 0:
             kv_all = ops.scene_kv(x1, W.ctx_unit, W.wkv_all, EPS)
@@ -986,42 +958,19 @@ class RenderFormer:
 
     def _encode_checked(self, sc: EncodedScene, log_encode: bool):
         """_encode under a range word of its own, resolved before returning (the caller holds sc.lock)."""
-        from ._lib import DeviceError
         if not (self.operands == "f16" and self.range_check != "off"):  # (stage 1 has no other fp16 writer)
             return self._encode(sc, log_encode)
-        lib = _load_lib()
-        with self._range_lock:
-            word = self._range_free.pop() if self._range_free else None
-        if word is None:
-            h = ctypes.c_void_p()
-            if lib.rf_range_word_new(ctypes.byref(h)) != 0:
-                raise RuntimeError(f"rf_range_word_new: {lib.rf_last_error().decode(errors='replace')}")
-            word = h.value
-        lib.rf_range_word_clear(word)
-        lib.rf_range_word_bind(word)
-        try:
+        with self._guard.bound() as word:
             self._encode(sc, log_encode)
-        except BaseException:
-            lib.rf_range_word_bind(None)
-            torch.cuda.current_stream().synchronize()
-            with self._range_lock:
-                self._range_free.append(word)
-            raise
-        lib.rf_range_word_bind(None)
         sc.event.synchronize()
-        code = int(lib.rf_range_word_read(word))
-        with self._range_lock:
-            self._range_free.append(word)
+        code, what = self._guard.take(word)
         if not code:
             return
-        what = [n for n, bit in (("GEMM", 1), ("RMSNorm", 2), ("attention", 4), ("DPT plane", 8)) if code & bit]
         if self.range_check == "deferred":
-            raise DeviceError(f"fp16 operand overflow (range code {code}: |x| > 65504 in an fp16 {'/'.join(what)} "
-                              "output) while encoding a scene -- this checkpoint's activations exceed fp16's range: "
-                              "encode with operands='bf16' (RF_OPERANDS=bf16), or range_check='sync' / 'lazy' "
-                              "(encodes such a scene again)")
+            raise deferred_error(code, what, "encode with operands='bf16' (RF_OPERANDS=bf16), or range_check='sync' "
+                                 "/ 'lazy' (encodes such a scene again)", where=" while encoding a scene")
         self._fall_back(code, what, "scene is encoded again", stacklevel=5)
-        self._guarded_replay(lambda: self._encode(sc, False))  # (the texture is log-encoded already)
+        self._guard.replay(lambda: self._encode(sc, False))  # (the texture is log-encoded already)
 
     def _check_handle(self, sc: EncodedScene):
         if not isinstance(sc, EncodedScene):
@@ -1067,20 +1016,14 @@ class RenderFormer:
         with torch.cuda.device(self._device):
             run = lambda: self._render_encoded(scene, c2w, fov, layout[:2], intrinsics=intrinsics,  # noqa: E731
                                                overscan=overscan)
-            return self._guarded(run, run, (c2w, fov if intrinsics is None else intrinsics))
+            return self._guard.run(run, run, (c2w, fov if intrinsics is None else intrinsics))
 
     def _render_encoded(self, sc: EncodedScene, c2w, fov, resolution, *, intrinsics=None, overscan=False):
-        cfg, dev = self.config, self._device
         self._check_handle(sc)
-        cam, cam_name = (fov, "fov") if intrinsics is None else (intrinsics, "intrinsics")
-        for t, n in ((c2w, "c2w"), (cam, cam_name)):
-            if t.device != dev:
-                raise ValueError(f"{n} must be on {dev} (got {t.device})")
-        B, V = c2w.shape[:2]
-        if B != sc.batch_size:
-            raise ValueError(f"c2w has batch size {B}, the encoded scene {sc.batch_size}")
-        H, W, Hp, Wp, _, _ = frame_layout(cfg, resolution, overscan)  # (the entry point checked it)
-        cut = lambda t, a, b: None if t is None else t[:, a:b]  # noqa: E731
+        self._on_device([(c2w, "c2w"), (fov, "fov") if intrinsics is None else (intrinsics, "intrinsics")])
+        if c2w.shape[0] != sc.batch_size:
+            raise ValueError(f"c2w has batch size {c2w.shape[0]}, the encoded scene {sc.batch_size}")
+        _, _, Hp, Wp, _, _ = frame_layout(self.config, resolution, overscan)  # (the entry point checked it)
         self._refresh(sc)
         with sc.lock:
             x1, kv_all, tris, ev, st = sc.x1, sc.kv_all, sc.tris, sc.event, sc.stream
@@ -1090,109 +1033,14 @@ class RenderFormer:
             for t in (x1, kv_all, tris):
                 if t is not None:
                     t.record_stream(cur)
-        chunk = V if not self.view_chunk else min(V, int(self.view_chunk))
-        out = None
-        for v0 in range(0, V, chunk):
-            v1 = min(V, v0 + chunk)
-            plan = self._plan_host(sc.mask_host, v1 - v0, (Hp, Wp))
-            o = self._views(plan, x1, tris, c2w[:, v0:v1], cut(fov, v0, v1), resolution, kv_all,
-                            intrinsics=cut(intrinsics, v0, v1), overscan=overscan)
-            o = o.view(B, v1 - v0, H, W, -1)
-            if v1 - v0 == V:
-                return o
-            if out is None:
-                out = torch.empty(B, V, *o.shape[2:], dtype=o.dtype, device=dev)
-            out[:, v0:v1] = o
-        return out
+        return self._view_chunks(lambda n: self._plan_host(sc.mask_host, n, (Hp, Wp)), x1, tris, c2w, fov, resolution,
+                                 kv_all, intrinsics=intrinsics, overscan=overscan)
 
     # ------------------------------------------------------------------ fp16 range check
-    def _range_active(self) -> bool:
-        return (self.operands == "f16" or self.dpt_precision == "f16") and self.range_check != "off"
-
-    def _guarded(self, run, replay, inputs):
-        """Run one render under a range word of its own; resolve it now (sync) or later (lazy / deferred)."""
-        if not self._range_active():
-            return run()
-        self._range_poll()
-        lib = _load_lib()
-        with self._range_lock:
-            word = self._range_free.pop() if self._range_free else None
-        if word is None:
-            h = ctypes.c_void_p()
-            if lib.rf_range_word_new(ctypes.byref(h)) != 0:
-                raise RuntimeError(f"rf_range_word_new: {lib.rf_last_error().decode(errors='replace')}")
-            word = h.value
-        lib.rf_range_word_clear(word)
-        lib.rf_range_word_bind(word)
-        try:
-            out = run()
-        except BaseException:
-            # a refused launch (validation / DeviceError): whatever did run reads the word only on this stream
-            lib.rf_range_word_bind(None)
-            torch.cuda.current_stream().synchronize()
-            with self._range_lock:
-                self._range_free.append(word)
-            raise
-        lib.rf_range_word_bind(None)
-        stream = torch.cuda.current_stream()
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        fr = _Frame(word, ev, stream, out, replay, inputs)
-        if self.range_check == "sync":
-            self._range_resolve(fr, wait=True)
-            return out
-        oldest = None
-        with self._range_lock:
-            self._range_pending.append(fr)
-            if len(self._range_pending) > RANGE_WORDS_MAX:
-                oldest = self._range_pending.pop(0)
-        if oldest is not None:
-            self._range_resolve(oldest, wait=True)
-        return out
-
-    def _range_poll(self):
-        """Resolve (oldest first) the pending frames whose end event has completed: no host wait."""
-        while True:
-            with self._range_lock:
-                if not (self._range_pending and self._range_pending[0].event.query()):
-                    return
-                fr = self._range_pending.pop(0)
-            self._range_resolve(fr, wait=False)
-
-    def _range_resolve(self, fr: _Frame, wait: bool) -> bool:
-        """Read a frame's word (after its end event); on an overflow fall back and re-render it in place (lazy /
-        sync) or raise DeviceError (deferred).  Returns True if the frame was rendered again.  The caller has taken
-        ``fr`` off the pending list, so no other thread resolves it."""
-        from ._lib import DeviceError
-        if wait:
-            fr.event.synchronize()
-        lib = _load_lib()
-        code = int(lib.rf_range_word_read(fr.word))
-        with self._range_lock:
-            self._range_free.append(fr.word)
-        if not code:
-            return False
-        what = [n for n, bit in (("GEMM", 1), ("RMSNorm", 2), ("attention", 4), ("DPT plane", 8)) if code & bit]
-        if self.range_check == "deferred":
-            raise DeviceError(f"fp16 operand overflow (range code {code}: |x| > 65504 in an fp16 {'/'.join(what)} "
-                              "output) -- this checkpoint's activations exceed fp16's range: render with "
-                              "operands='bf16' (RF_OPERANDS=bf16) and dpt_precision='bf16x3', or range_check='sync' "
-                              "/ 'lazy' (re-renders such frames)")
-        if any(t._version != v for t, v in zip(fr.inputs, fr.versions)):
-            raise DeviceError(f"fp16 operand overflow (range code {code}) in a frame whose inputs were modified in "
-                              "place before it could be rendered again: call resolve(out) / check_range() before "
-                              "reusing input buffers, or use range_check='sync'")
-        self._fall_back(code, what, "frame is rendered again", stacklevel=5)
-        with torch.cuda.device(self._device), torch.cuda.stream(fr.stream):
-            new = self._guarded_replay(fr.replay)
-            fr.out.copy_(new.view_as(fr.out))
-        fr.out._rf_rerendered = True  # resolve(out) reports it even when a later render's poll did the re-render
-        return True
-
     def _fall_back(self, code: int, what, redo: str, stacklevel: int):
         """Move the model to the operands an fp16 overflow (range code ``code``) asks for, and warn."""
         import warnings
-        with self._range_lock:
+        with self._guard.lock:
             # projections and attention (codes 1/2/4) -> bf16 operands; the DPT planes (code 8) -> bf16x3, and a
             # stage-1 or stage-2 overflow reaches the DPT as inf too, so it sets 8 as well
             operands = "bf16" if code & 7 else self.operands
@@ -1202,7 +1050,7 @@ class RenderFormer:
                 # the old tensors into the caching allocator of the stream they were made on; frames still in flight
                 # on other streams read them, so wait for every pending frame first (an overflow is rare: this wait
                 # is the fallback path's only cost)
-                for p in self._range_pending:
+                for p in self._guard.pending:
                     p.event.synchronize()
                 self.operands, self.dpt_precision = operands, dpt
                 self._w = _DeviceWeights(self.config, self._sd, self._device, self.dpt_precision, self.operands)
@@ -1212,79 +1060,26 @@ class RenderFormer:
                       f"{self.operands} projection operands and {self.dpt_precision} DPT planes from now on",
                       PrecisionWarning, stacklevel=stacklevel)
 
-    def _guarded_replay(self, replay):
-        """The re-render after a fallback, checked at once: an overflow that survives it is an error."""
-        from ._lib import DeviceError
-        if not self._range_active():
-            return replay()
-        lib = _load_lib()
-        h = ctypes.c_void_p()
-        if lib.rf_range_word_new(ctypes.byref(h)) != 0:
-            raise RuntimeError(f"rf_range_word_new: {lib.rf_last_error().decode(errors='replace')}")
-        lib.rf_range_word_bind(h.value)
-        try:
-            out = replay()
-        finally:
-            lib.rf_range_word_bind(None)
-        torch.cuda.current_stream().synchronize()
-        code = int(lib.rf_range_word_read(h.value))
-        lib.rf_range_word_free(h.value)
-        if code:
-            raise DeviceError(f"fp16 overflow (range code {code}) persists after the bf16 fallback")
-        return out
-
     def resolve(self, out: Optional[torch.Tensor] = None) -> bool:
         """Finish the range check of the frame whose output is ``out`` (every pending frame if None), waiting for
         it: afterwards ``out`` holds the final frame (rendered again if it overflowed fp16).  Returns True if a
         frame was rendered again.  batch_infer.py calls it where it already waits for the frame's copy; in the
         default "sync" mode render has already done it and this only reports."""
-        with self._range_lock:
-            keep, done = [], []
-            for fr in self._range_pending:
-                (done if out is None or fr.out is out else keep).append(fr)
-            self._range_pending = keep
-        for fr in done:
-            self._range_resolve(fr, wait=True)
-        redo = False
-        for t in ([fr.out for fr in done] if out is None else [out]):
-            if getattr(t, "_rf_rerendered", False):
-                t._rf_rerendered = False
-                redo = True
-        return redo
+        return self._guard.resolve(out)
 
     def check_range(self):
         """Resolve every pending frame (waiting for each): deferred mode raises DeviceError for an overflowed frame,
         lazy mode re-renders it in place.  Call before reading frames whose range check is pending."""
-        with self._range_lock:
-            pending, self._range_pending = self._range_pending, []
-        for i, fr in enumerate(pending):
-            try:
-                self._range_resolve(fr, wait=True)
-            except BaseException:
-                for rest in pending[i + 1:]:  # the others' words stay usable
-                    rest.event.synchronize()
-                    with self._range_lock:
-                        self._range_free.append(rest.word)
-                raise
+        self._guard.check_range()
 
     def close(self):
         """Release the model's host-mapped range words: pending frames are waited for first.  Called
         by ``__del__``; the model stays usable (new words are allocated on the next render)."""
-        lib = None
-        with self._range_lock:
-            words = list(self._range_free)
-            for fr in self._range_pending:
-                fr.event.synchronize()
-                words.append(fr.word)
-            self._range_free, self._range_pending = [], []
-        for w in words:
-            if lib is None:
-                lib = _load_lib()
-            lib.rf_range_word_free(w)
+        self._guard.close()
 
     def __del__(self):
         try:
-            if getattr(self, "_range_lock", None) is not None:
+            if getattr(self, "_guard", None) is not None:
                 self.close()
         except Exception:  # interpreter shutdown: the library or torch may already be gone
             pass
@@ -1299,38 +1094,53 @@ class RenderFormer:
 
     def _render_views(self, triangles, texture, mask, vn, c2w, fov, resolution, log_encode, *, intrinsics=None,
                       overscan=False):
-        cfg, dev = self.config, self._device
-        B, V = c2w.shape[:2]
-        for t, n in ((triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn"), (c2w, "c2w"),
-                     (fov, "fov") if intrinsics is None else (intrinsics, "intrinsics")):
-            if t.device != dev:
-                raise ValueError(f"{n} must be on {dev} (got {t.device})")
-        H, W, Hp, Wp, _, _ = frame_layout(cfg, resolution, overscan)  # (the entry point checked it)
-        padded = (Hp, Wp)  # what the plans are built for, and cached by
-        cut = lambda t, a, b: None if t is None else t[:, a:b]  # noqa: E731
-        # views in chunks of at most view_chunk (stage 1 once): every chunk runs the same launch sequence on the
-        # same problem tables whatever the other views are, so a view's image does not depend on how the views of
-        # a scene are batched or split over ranks (bench.py c5)
-        chunk = V if not self.view_chunk else min(V, int(self.view_chunk))
-        plan = self._plan(mask, chunk, padded)
+        self._on_device([(triangles, "triangles"), (texture, "texture"), (mask, "mask"), (vn, "vn"), (c2w, "c2w"),
+                         (fov, "fov") if intrinsics is None else (intrinsics, "intrinsics")])
+        _, _, Hp, Wp, _, _ = frame_layout(self.config, resolution, overscan)  # (the entry point checked it)
+        # (plans are built for, and cached by, the padded frame; a mask tensor seen before is not read back)
+        plan_of = lambda n: self._plan(mask, n, (Hp, Wp))  # noqa: E731
+        tris, x1 = self._scene_front(plan_of(self._chunk(c2w.shape[1])), triangles, texture, vn, log_encode)
+        return self._view_chunks(plan_of, x1, tris, c2w, fov, resolution, intrinsics=intrinsics, overscan=overscan)
+
+    def _chunk(self, V: int) -> int:
+        return V if not self.view_chunk else min(V, int(self.view_chunk))
+
+    def _on_device(self, tensors):
+        """Every tensor of the ``(tensor, name)`` pairs is on the model's device."""
+        for t, n in tensors:
+            if t.device != self._device:
+                raise ValueError(f"{n} must be on {self._device} (got {t.device})")
+
+    def _scene_front(self, plan: _Plan, triangles, texture, vn, log_encode: bool):
+        """The camera-independent front of a render: packed triangles, their embedding and positions, stage 1.
+        Returns (tris [B, N, 9] f32, x1 [T1, D] f32)."""
+        B = plan.B
         tris = triangles.reshape(B, -1, 9).float().contiguous()
         x1 = self._embed_triangles(plan, texture, vn.reshape(B, -1, 9).float().contiguous(), log_encode)
-        pos1 = torch.empty(plan.T1, 9, dtype=torch.float32, device=dev)
-        ops.scene_pos(tris, plan.valid_flat, plan.scene_off, None, B, 1, cfg.num_register_tokens, pos1, plan.cu1,
-                      max(plan.counts))
-        x1 = self._stage1(plan, x1, pos1)
-        if chunk == V:
-            return self._views(plan, x1, tris, c2w, fov, resolution, intrinsics=intrinsics,
-                               overscan=overscan).view(B, V, H, W, -1)
+        pos1 = torch.empty(plan.T1, 9, dtype=torch.float32, device=self._device)
+        ops.scene_pos(tris, plan.valid_flat, plan.scene_off, None, B, 1, self.config.num_register_tokens, pos1,
+                      plan.cu1, max(plan.counts))
+        return tris, self._stage1(plan, x1, pos1)
+
+    def _view_chunks(self, plan_of, x1, tris, c2w, fov, resolution, kv_all=None, *, intrinsics=None, overscan=False):
+        """Stage 2 + DPT (``_views``) over the views in chunks of at most view_chunk, as [B, V, H, W, C];
+        ``plan_of(n)`` is the plan of a chunk of n views.  Every chunk runs the same launch sequence on the same
+        problem tables whatever the other views are, so a view's image does not depend on how the views of a scene
+        are batched or split over ranks (bench.py c5)."""
+        B, V = c2w.shape[:2]
+        H, W = frame_layout(self.config, resolution, overscan)[:2]
+        cut = lambda t, a, b: None if t is None else t[:, a:b]  # noqa: E731
+        chunk = self._chunk(V)
         out = None
         for v0 in range(0, V, chunk):
             v1 = min(V, v0 + chunk)
-            pc = plan if v1 - v0 == chunk else self._plan(mask, v1 - v0, padded)
-            o = self._views(pc, x1, tris, c2w[:, v0:v1], cut(fov, v0, v1), resolution,
+            o = self._views(plan_of(v1 - v0), x1, tris, c2w[:, v0:v1], cut(fov, v0, v1), resolution, kv_all,
                             intrinsics=cut(intrinsics, v0, v1), overscan=overscan)
             o = o.view(B, v1 - v0, H, W, -1)
+            if v1 - v0 == V:
+                return o
             if out is None:
-                out = torch.empty(B, V, *o.shape[2:], dtype=o.dtype, device=dev)
+                out = torch.empty(B, V, *o.shape[2:], dtype=o.dtype, device=self._device)
             out[:, v0:v1] = o
         return out
 
@@ -1373,20 +1183,14 @@ class RenderFormer:
         self._require()
         with torch.cuda.device(self._device):
             args = (tri_vpos_list, texture_patch_list, valid_mask, vns, rays_o, rays_d, tri_vpos_view_tf)
-            return self._guarded(lambda: self._forward(*args), lambda: self._forward(*args), args)
+            return self._guard.run(lambda: self._forward(*args), lambda: self._forward(*args), args)
 
     def _forward(self, tri_vpos_list, texture_patch_list, valid_mask, vns, rays_o, rays_d, tri_vpos_view_tf):
         cfg, dev = self.config, self._device
         B, V = rays_o.shape[:2]
         H, W = frame_size(cfg, tuple(rays_d.shape[2:4]))
         plan = self._plan(valid_mask, V, (H, W))
-        tris = tri_vpos_list.reshape(B, -1, 9).float().contiguous()
-        x1 = self._embed_triangles(plan, texture_patch_list.float().contiguous(),
-                                   vns.reshape(B, -1, 9).float().contiguous(), log_encode=False)
-        pos1 = torch.empty(plan.T1, 9, dtype=torch.float32, device=dev)
-        ops.scene_pos(tris, plan.valid_flat, plan.scene_off, None, B, 1, cfg.num_register_tokens, pos1, plan.cu1,
-                      max(plan.counts))
-        x1 = self._stage1(plan, x1, pos1)
+        _, x1 = self._scene_front(plan, tri_vpos_list, texture_patch_list.float().contiguous(), vns, log_encode=False)
         P = B * V
         ray_in = torch.empty(P * plan.R, 3 * cfg.patch_size ** 2, dtype=self._w.half, device=dev)
         ops.patchify_rays(rays_d.reshape(P, H, W, 3).float().contiguous(), cfg.patch_size, ray_in)

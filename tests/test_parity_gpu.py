@@ -602,7 +602,7 @@ def test_lazy_fallback_waits_for_frames_in_flight():
         print(f"frame {name}: rel L2 {err:.3e}")
         assert torch.isfinite(o).all() and err < HDR_TOL
     pipe.model.close()
-    assert not pipe.model._range_free and not pipe.model._range_pending
+    assert not pipe.model._guard.free and not pipe.model._guard.pending
 
 
 def test_f16_overflow_deferred_check_raises():
