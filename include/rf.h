@@ -45,6 +45,10 @@
  *                      trace: nearest hit of every pixel's ray with the scene's triangles (depth, triangle id,
  *                      barycentrics, alpha) and the hit's shading normal and diffuse albedo.  The reference has no
  *                      counterpart (its frames are radiance only); the rays are rf_ray_tokens_cam's
+ *   rf_pose_scene      scene_processor/scene_mesh.py:41-55 (rotate, scale, translate an object) applied to a converted
+ *                      scene's triangles and normals per frame, with to_h5.py:47-61's per-triangle material constants
+ *                      gathered from a table; rf_texture_rows is rf_texture_scan for those constants ([rows, C]
+ *                      instead of [rows, C, 32, 32]: nothing to prove, nothing expanded)
  *   rf_conv2d_bf16x3   DPT nn.Conv2d (dpt.py:44-52, 69-72, 124-125, 184-192, 208-213, 232-240; aten conv2d) with
  *                      the ResidualConvUnit SiLU/skip (dpt.py:86-92) and fusion sum (:141-143) fused; FINAL mode
  *                      also fuses output_conv2 SiLU + 1x1 (dpt.py:234-240), ELU and the log decode
@@ -88,7 +92,8 @@ extern "C" {
  * Still 16 with rf_ray_tokens_cam / rf_hdr_output_win / rf_frame_window: three new symbols.
  * Still 16 with rf_conv_plan_query: a new symbol.
  * Still 16 with rf_tonemap_ldr8: a new symbol.
- * Still 16 with rf_primary_hits / rf_gbuffer_shade: two new symbols. */
+ * Still 16 with rf_primary_hits / rf_gbuffer_shade: two new symbols.
+ * Still 16 with rf_pose_scene / rf_texture_rows: two new symbols. */
 #define RF_ABI_VERSION 16
 
 /* GEMM epilogues */
@@ -531,6 +536,35 @@ int rf_primary_hits(const float* tris, const int32_t* valid_idx, const int32_t* 
 int rf_gbuffer_shade(const int32_t* tri_id, const float* bary, const float* vn, const float* texture,
                      int64_t tex_row_stride, int64_t tex_chan_stride, int n_tris_per_scene, int n_scenes,
                      int64_t pix_per_scene, uint8_t* alpha, float* normal, float* albedo, void* stream);
+
+/* Pose a rest-pose scene: per-object affine transforms and a material table -> the triangles, vertex normals and
+ * material rows of one frame, in one launch over the n_scenes * n_tris_per_scene triangle rows (rf_pose_scene).
+ * Inputs: tris, vn f32 [rows, 9] (three vertices / normals of three floats); object_id, material_id int32 [rows];
+ * xf f32: the 3 x 4 matrix [A | t] of object o in scene b is the 12 row-major floats at xf + (b * n_objects + o) * ld_xf
+ * (ld_xf = 12: [B, K, 3, 4]; ld_xf = 16: a contiguous [B, K, 4, 4] whose last row is never read); materials f32
+ * [n_scenes, n_materials, channels], channels <= 16.  Outputs: tris_out, vn_out f32 [rows, 9], tex_out f32 [rows, channels]
+ * (the [B, N, C] texture form of rf_texture_rows / rf_gbuffer_shade).  An output may be its own input (the same pointer).
+ * Row r of scene b = r / n_tris_per_scene, o = object_id[r]:
+ *   - padding (o < 0; also an o >= n_objects, through which nothing is read): tris and vn are copied bit for bit, the
+ *     material row is zeros;
+ *   - vertices p' = A p + t in fp32, per coordinate i: fmaf(a_i2, p_2, fmaf(a_i1, p_1, fmaf(a_i0, p_0, t_i)));
+ *   - normals g = s cof(A) n with cof(A)'s rows a1 x a2, a2 x a0, a0 x a1 (a_i the rows of A) and s = -1 if det A < 0
+ *     else +1, n' = g / |g| if |g| > 0 else (0, 0, 0): A^-T n up to a positive factor, so correct under non-uniform
+ *     scale, on the outward side under a mirror, zero for a zero normal and finite for a singular A.  cof(A), g and the
+ *     normalisation are evaluated in fp64 from the fp32 inputs and n' is rounded to fp32 once (2^-24 relative);
+ *   - tex_out[r, :] = materials[b, material_id[r], :], a copy (zeros for a material_id outside 0 .. n_materials - 1).
+ * Refused before any launch: a null pointer, ld_xf other than 12 or 16, channels > 16, a negative count,
+ * n_scenes * n_tris_per_scene or n_scenes * n_materials >= 2^31.  No rows: nothing is launched. */
+int rf_pose_scene(const float* tris, const float* vn, const int32_t* object_id, const int32_t* material_id,
+                  const float* xf, int ld_xf, const float* materials, int n_scenes, int n_tris_per_scene, int n_objects,
+                  int n_materials, int channels, float* tris_out, float* vn_out, float* tex_out, void* stream);
+/* rf_texture_scan for the compact texture f32 [n_rows, channels] (one constant per triangle and channel, channels <=
+ * 16): channels >= channels - log_channels are log10(x + 1) encoded IN PLACE for every row, padded rows included (the
+ * expression of rf_texture_scan, so the same bits as the constant it extracts from an expanded patch), and rows with
+ * dst_row[r] >= 0 (dst_row NULL: every row r) are written to coef[dst_row[r] * ldc + c]: the operand of
+ * rf_texture_linear, with a flag word that stays 0.  There is no form to prove and no flag. */
+int rf_texture_rows(float* texture, int64_t n_rows, int channels, int log_channels, const int32_t* dst_row,
+                    float* coef, int64_t ldc, void* stream);
 
 /* DPT convolutions on the GEMM engine.  Activations are NHWC; a convolution reads its input as two
  * bf16 planes (hi = bf16(x), lo = bf16(x - hi); channel stride cin_pad, padded channels zero) and its

@@ -7,7 +7,8 @@ eager-PyTorch fallback for the compute path.
 """
 from .config import RenderFormerConfig
 
-__all__ = ["RenderFormerRenderingPipeline", "RenderFormer", "RenderFormerConfig", "EncodedScene"]
+__all__ = ["RenderFormerRenderingPipeline", "RenderFormer", "RenderFormerConfig", "EncodedScene", "SceneRig",
+           "PosedScene", "trs"]
 
 
 def __getattr__(name):
@@ -17,6 +18,9 @@ def __getattr__(name):
     if name == "EncodedScene":
         from .model import EncodedScene
         return EncodedScene
+    if name in ("SceneRig", "PosedScene", "trs"):
+        from . import rig
+        return getattr(rig, name)
     if name == "RenderFormerRenderingPipeline":
         from .pipeline import RenderFormerRenderingPipeline
         return RenderFormerRenderingPipeline

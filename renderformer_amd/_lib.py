@@ -79,6 +79,8 @@ SIGNATURES = {
     "rf_tonemap_ldr8": [_P, _P, _P, _L, _I, _F, _P],
     "rf_primary_hits": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "rf_gbuffer_shade": [_P, _P, _P, _P, _L, _L, _I, _I, _L, _P, _P, _P, _P],
+    "rf_pose_scene": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "rf_texture_rows": [_P, _L, _I, _I, _P, _P, _L, _P],
     "rf_ray_tokens": [_P, _P, _I, _I, _I, _P, _P, _P],
     "rf_patchify_rays": [_P, _I, _I, _I, _P, _P],
     "rf_scene_pos": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _L, _P],

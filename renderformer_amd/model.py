@@ -103,6 +103,9 @@ class _DeviceWeights:
         # texture fast-path flags by frame parity: frame i raises tex_flags[i % 2] and its scan clears the other
         # one for frame i + 1 (no reset launch in the frame; rf_texture_scan2)
         self.tex_flags = torch.zeros(2, dtype=torch.int32, device=device)
+        # the flag word of compact [B, N, C] textures (ops.texture_rows): never raised, and apart from the parity
+        # pair above, so compact and expanded frames alternate on one model in any order
+        self.tex_rows_flag = torch.zeros(1, dtype=torch.int32, device=device)
         # identity camera transforms per view count (read-only; built on the host and copied synchronously, so a
         # render on another stream never sees it half-written): no fill kernels between stage 1 and stage 2
         self.eyes: Dict[int, torch.Tensor] = {}
@@ -598,9 +601,25 @@ class RenderFormer:
         D = cfg.latent_dim
         kt = cfg.texture_channels * cfg.texture_encode_patch_size ** 2
         log_ch = 3 if log_encode else 0
-        tex_in = torch.empty(plan.T_tri, kt, dtype=torch.bfloat16, device=dev)
         tex_lin = torch.empty(plan.T_tri, D, dtype=torch.float32, device=dev)
-        fast = (self._tex_fast and plan.T_tri > 0 and W.tex_wsum is not None and texture.dim() == 5
+        rows = cfg.texture_encode_patch_size != 1 and texture.dim() == 3
+        if rows:
+            # material rows [B, N, C]: one constant per triangle and channel, the form the scan below proves of an
+            # expanded texture.  Nothing to prove here: the constants go straight to the C-wide product (no pack, no
+            # K = C * 1024 GEMM), whatever RF_TEX_FAST says (it chooses between the two paths of expanded textures)
+            if texture.shape[2] != cfg.texture_channels:
+                raise ValueError(f"a [B, N, C] texture needs C = texture_channels = {cfg.texture_channels}, got "
+                                 f"{tuple(texture.shape)}")
+            if W.tex_wsum is None:
+                raise ValueError("a [B, N, C] texture (one constant per triangle and channel) needs the mask-summed "
+                                 f"encoder weights, which exist for texture_encode_patch_size 32 only (this model's is "
+                                 f"{cfg.texture_encode_patch_size}): pass the expanded [B, N, C, p, p] texture")
+            coef = torch.empty(max(plan.T_tri, 1), 16, dtype=torch.float32, device=dev)  # (no valid row: encode only)
+            ops.texture_rows(texture, log_ch, plan.dst_row, coef)
+            if plan.T_tri:
+                ops.texture_linear(coef, W.tex_wsum, W.tex_b, tex_lin, W.tex_rows_flag)
+        tex_in = None if rows else torch.empty(plan.T_tri, kt, dtype=torch.bfloat16, device=dev)
+        fast = (not rows and self._tex_fast and plan.T_tri > 0 and W.tex_wsum is not None and texture.dim() == 5
                 and tuple(texture.shape[2:]) == (cfg.texture_channels, 32, 32))
         if fast:
             # to_h5-format textures: one scan proves the per-channel-constant form and
@@ -613,7 +632,7 @@ class RenderFormer:
             ops.texture_linear(coef, W.tex_wsum, W.tex_b, tex_lin, flag)
             ops.texture_pack_if(flag, texture, 0, plan.dst_row, tex_in)
             ops.gemm(tex_in, W.tex_w, tex_lin, W.tex_b, ops.EPI_F32, flag=flag)
-        else:
+        elif not rows:
             ops.texture_pack(texture, log_ch, plan.dst_row, tex_in)
             if plan.T_tri:
                 ops.gemm(tex_in, W.tex_w, tex_lin, W.tex_b, ops.EPI_F32)

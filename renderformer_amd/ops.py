@@ -792,6 +792,57 @@ def texture_linear(coef: torch.Tensor, wsum: torch.Tensor, bias: Optional[torch.
     return out
 
 
+def texture_rows(texture: torch.Tensor, log_channels: int, dst_row: Optional[torch.Tensor], coef: torch.Tensor):
+    """The compact counterpart of texture_scan (rf_texture_rows): ``texture`` f32 [B, N, C] (or [rows, C]), one
+    constant per triangle and channel, is log-encoded in place (its last ``log_channels`` channels, every row) and
+    its valid rows are scattered to ``coef`` [T, >= C], the operand of texture_linear."""
+    _dev(texture, torch.float32, "texture")
+    _dev(coef, torch.float32, "coef")
+    _check(texture.is_contiguous() and texture.dim() in (2, 3), "texture_rows: texture must be contiguous [B, N, C]")
+    c = texture.shape[-1]
+    _check(coef.dim() == 2 and coef.shape[1] >= c, "texture_rows: coef must be [T, >= C]")
+    if dst_row is not None:
+        _dev(dst_row, torch.int32, "dst_row")
+        _check(dst_row.numel() == texture.numel() // max(c, 1), "texture_rows: one dst_row per texture row")
+    call("rf_texture_rows", ptr(texture), texture.numel() // max(c, 1), c, log_channels, ptr(dst_row), ptr(coef),
+         coef.stride(0), stream())
+    return coef
+
+
+def pose_scene(tris: torch.Tensor, vn: torch.Tensor, object_id: torch.Tensor, material_id: torch.Tensor,
+               xf: torch.Tensor, materials: torch.Tensor, out=None):
+    """rf_pose_scene: rest ``tris`` / ``vn`` f32 [B, N, 9] (or [B, N, 3, 3]), ``object_id`` / ``material_id`` int32
+    [B, N] (-1: padding), ``xf`` f32 [B, K, 3, 4] or [B, K, 4, 4], ``materials`` f32 [B, M, C <= 16] -> (triangles,
+    vn, texture [B, N, C]) of the posed scene, in one launch.  The ids are NOT checked here (renderformer_amd.rig
+    validates a rig once, on the host); an id outside its table makes the row a padding row.  ``out``: three
+    contiguous tensors of the results' shapes to write."""
+    for t, n in ((tris, "tris"), (vn, "vn"), (xf, "xf"), (materials, "materials")):
+        _dev(t, torch.float32, n)
+        _check(t.is_contiguous(), f"pose_scene: {n} must be contiguous")
+    for t, n in ((object_id, "object_id"), (material_id, "material_id")):
+        _dev(t, torch.int32, n)
+        _check(t.is_contiguous() and t.dim() == 2, f"pose_scene: {n} must be contiguous [B, N]")
+    B, N = object_id.shape
+    _check(tuple(material_id.shape) == (B, N), "pose_scene: object_id and material_id differ in shape")
+    _check(tris.shape[:2] == (B, N) and tris.numel() == B * N * 9 and tuple(vn.shape) == tuple(tris.shape),
+           f"pose_scene: tris and vn must be [{B}, {N}, 9] or [{B}, {N}, 3, 3]")
+    _check(xf.dim() == 4 and xf.shape[0] == B and tuple(xf.shape[2:]) in ((3, 4), (4, 4)),
+           f"pose_scene: xf must be [{B}, K, 3, 4] or [{B}, K, 4, 4], got {tuple(xf.shape)}")
+    _check(materials.dim() == 3 and materials.shape[0] == B and materials.shape[2] <= 16,
+           f"pose_scene: materials must be [{B}, M, C <= 16], got {tuple(materials.shape)}")
+    K, M, C = xf.shape[1], materials.shape[1], materials.shape[2]
+    shapes = (tuple(tris.shape), tuple(tris.shape), (B, N, C))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=tris.device) for s in shapes)
+    _check(len(out) == 3, "pose_scene: out must hold (triangles, vn, texture)")
+    for t, s in zip(out, shapes):
+        _check(t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == s and t.is_contiguous(),
+               f"pose_scene: out tensors must be contiguous float32 device tensors {shapes}")
+    call("rf_pose_scene", ptr(tris), ptr(vn), ptr(object_id), ptr(material_id), ptr(xf), xf.shape[2] * 4,
+         ptr(materials), B, N, K, M, C, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream())
+    return tuple(out)
+
+
 def _dt(out: torch.Tensor) -> int:
     _check(out.dtype in HALF, "16-bit output must be bf16 or fp16")
     return DT_F16 if out.dtype == torch.float16 else DT_BF16

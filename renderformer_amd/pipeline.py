@@ -77,6 +77,9 @@ class RenderFormerRenderingPipeline:
                           PrecisionWarning, stacklevel=stacklevel)
 
     def _texture(self, texture):
+        """The texture as the model takes it: the reference's [bs, N, C, p, p], or material rows [bs, N, C] (one
+        constant per triangle and channel: what ``pose`` returns); float32 and contiguous either way, since it is
+        log-encoded in place."""
         if self.config.texture_encode_patch_size == 1 and texture.dim() == 5:
             texture = texture[:, :, :, 0, 0].contiguous()
         if not texture.is_contiguous():
@@ -134,6 +137,51 @@ class RenderFormerRenderingPipeline:
         out = self.model.render_encoded(scene, c2w, fov, resolution, intrinsics=intrinsics, overscan=overscan)
         self.last_precision = {"requested": str(torch_dtype), "computed": self.model.precision}
         return out
+
+    def pose(self, rig, transforms, materials=None, *, out=None):
+        """Pose a rest-pose ``SceneRig`` (renderformer_amd.rig) for one frame, on the device: one HIP launch
+        (``ops.pose_scene``), no model weights.  Returns ``PosedScene(triangles, texture, mask, vn)``, which unpacks
+        into ``encode``, ``render`` and ``gbuffer``; its ``texture`` is the compact [B, N, C] form (one constant per
+        triangle and channel: no [B, N, C, 32, 32] tensor is made), NOT yet log-encoded -- ``render`` / ``encode``
+        do that in place, once, as for any texture, so pose again (or pass ``out=``) for the next frame.
+
+        ``transforms``: float32 [B, K, 3, 4] or [B, K, 4, 4] (the last row is ignored), contiguous, on the rig's
+        device: ``[A | t]`` per object, ``rig.transforms0`` being the config's own (``rig.trs`` builds one).
+        ``materials``: float32 [B, M, C] like ``rig.materials0`` (None: ``rig.materials0``).  ``out``: a previous
+        ``PosedScene`` of this rig whose buffers are written again.  Anything else raises ValueError.
+
+        Vertices go to ``A p + t``, normals to the normalised ``sign(det A) cof(A) n`` (right under non-uniform scale
+        and mirrors, zero for a zero normal, never NaN), padding rows pass through with a zero material row.  A rig
+        posed with its own ``transforms0`` / ``materials0`` reproduces the scene converter for every object that is
+        flat-shaded or uniformly scaled; for a smooth-shaded object under NON-uniform scale the converter measures
+        its 30-degree smoothing groups and angle weights after the transform, so its normals differ from the
+        geometrically transformed rest normals a rig gives."""
+        from . import ops
+        from .rig import PosedScene, SceneRig
+        if not isinstance(rig, SceneRig):
+            raise ValueError(f"pose needs a SceneRig, got {type(rig)}")
+        dev = rig.device
+        if dev.type != "cuda":
+            raise ValueError("pose: the rig must be on the HIP device (rig.to('cuda')); renderformer_amd.rig.pose_numpy is the CPU form")
+        B, K = rig.batch_size, len(rig.names)
+        if materials is None:
+            materials = rig.materials0
+        for t, n, shapes in ((transforms, "transforms", ((B, K, 3, 4), (B, K, 4, 4))),
+                             (materials, "materials", (tuple(rig.materials0.shape),))):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ValueError(f"pose: {n} must be a tensor on the rig's device {dev}")
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) not in shapes:
+                raise ValueError(f"pose: {n} must be contiguous float32 {' or '.join(map(str, shapes))}, got "
+                                 f"{t.dtype} {tuple(t.shape)}" + ("" if t.is_contiguous() else " (not contiguous)"))
+        bufs = None
+        if out is not None:
+            if not isinstance(out, PosedScene):
+                raise ValueError(f"pose: out must be a PosedScene of this rig, got {type(out)}")
+            bufs = (out.triangles, out.vn, out.texture)
+        with torch.cuda.device(dev):
+            tris, vn, tex = ops.pose_scene(rig.triangles, rig.vn, rig.object_id, rig.material_id, transforms,
+                                           materials, out=bufs)
+        return PosedScene(tris, tex, rig.mask, vn)
 
     def to_ldr(self, hdr: torch.Tensor, tone_mapper: str = "none", exposure: float = 0.0, out: torch.Tensor = None):
         """The 8-bit display frame of rendered HDR frames, made on the device (one HIP kernel, ``ops.tonemap_ldr8``):

@@ -347,6 +347,72 @@ def object_arrays(obj: ObjectConfig, scene_dir: str):
     return tris, vn, ch
 
 
+def transform_matrix(t: TransformConfig) -> np.ndarray:
+    """[3, 4] f64 ``[A | t]`` of transform_vertices after its normalisation: A = diag(scale) Rz Ry Rx."""
+    a = np.eye(3)
+    for axis, ang in enumerate(t.rotation):
+        a = _rotation(axis, ang) @ a
+    a = np.asarray(t.scale, dtype=np.float64)[:, None] * a
+    return np.concatenate([a, np.asarray(t.translation, dtype=np.float64)[:, None]], axis=1)
+
+
+def scene_rig(cfg: SceneConfig, scene_dir: str):
+    """The scene in its REST pose, for posing per frame (renderformer_amd.rig): what object_arrays does up to, but not
+    including, rotate / scale / translate -- load, optional unit-sphere normalisation, ``shade`` -- plus what a pose
+    needs to put it back.  A dict of
+      triangles, vn  [N, 3, 3] f64, the objects concatenated in the config's order (no 8-decimal rounding: that is the
+                     converter's export of the POSED mesh);
+      object_id      [N] int32, the index of each triangle's object in ``names``;
+      material_id    [N] int32, rows of ``materials``;
+      names          the K object names;
+      transforms     [K, 3, 4] f64, each object's own ``[A | t]`` (transform_matrix);
+      materials      [M, 13] f64, the converter's channels (diffuse through uint8, specular, roughness, the constant
+                     normal (0.5, 0.5, 1), emissive).  An object takes one row; one with ``rand_tri_diffuse_seed`` takes
+                     one row per colour group (per triangle or per shading group), so M >= K;
+      material_slots per object, the (first row, row count) it owns in ``materials``.
+    Posing this with ``transforms`` and ``materials`` reproduces scene_arrays for every object that is flat-shaded or
+    uniformly scaled; a smooth-shaded object under non-uniform scale differs in its normals (the converter groups and
+    weights the faces of the transformed mesh, a pose transforms the rest normals geometrically)."""
+    tris, vns, oid, mid, mats, xfs, slots = [], [], [], [], [], [], []
+    for k, obj in enumerate(cfg.objects.values()):
+        if obj.remesh:
+            raise NotImplementedError("remesh needs pymeshlab (scene_processor/remesh.py), which is not available")
+        v, f = load_obj(os.path.join(scene_dir, obj.mesh_path))
+        rest = dataclasses.replace(obj.transform, translation=[0.0, 0.0, 0.0], rotation=[0.0, 0.0, 0.0],
+                                   scale=[1.0, 1.0, 1.0])
+        v = transform_vertices(v, rest) if obj.transform.normalize else v
+        t, vn, gid = shade(v, f, obj.material.smooth_shading)
+        n = len(t)
+        m = obj.material
+        base = sum(len(c) for c in mats)
+        row = np.concatenate([np.zeros(3), np.asarray(m.specular, dtype=np.float64), [float(m.roughness)],
+                              [0.5, 0.5, 1.0], np.asarray(m.emissive, dtype=np.float64)])
+        if m.rand_tri_diffuse_seed is not None:  # object_arrays' draws, in its order
+            np.random.seed(m.rand_tri_diffuse_seed)
+            comp = np.arange(n) if m.random_diffuse_type == "per-triangle" else gid
+            n_comp = int(comp.max()) + 1 if n else 0
+            ch = np.repeat(row[None], n_comp, axis=0)
+            for c in range(n_comp):
+                ch[c, :3] = np.random.randint(0, math.ceil(256 * m.random_diffuse_max), (1, 3))[0] / 255.0
+            local = comp
+        else:
+            ch = row[None].copy()
+            ch[0, :3] = (np.array(m.diffuse) * 255.0).clip(0, 255).astype(int) / 255.0
+            local = np.zeros(n, dtype=np.int64)
+        tris.append(t)
+        vns.append(vn)
+        oid.append(np.full(n, k, dtype=np.int32))
+        mid.append((base + local).astype(np.int32))
+        mats.append(ch)
+        slots.append((base, len(ch)))
+        xfs.append(transform_matrix(obj.transform))
+    cat = lambda xs, shape: np.concatenate(xs) if xs else np.zeros(shape)  # noqa: E731
+    return {"triangles": cat(tris, (0, 3, 3)), "vn": cat(vns, (0, 3, 3)),
+            "object_id": cat(oid, (0,)).astype(np.int32), "material_id": cat(mid, (0,)).astype(np.int32),
+            "names": list(cfg.objects), "transforms": np.stack(xfs) if xfs else np.zeros((0, 3, 4)),
+            "materials": cat(mats, (0, 13)), "material_slots": slots}
+
+
 def scene_arrays(cfg: SceneConfig, scene_dir: str, size: int = 32):
     """The five HDF5 datasets of to_h5.py:87-92 (before their dtype casts)."""
     tris, vns, chs = [], [], []
